@@ -13,7 +13,21 @@ rank 0) and the barriers around the timed region.
 value = user-data bytes (k * L per stripe, counted once for the encode and
 once for the decode) of all ranks / max-over-ranks wall time, in GiB/s.
 
-Run: python bench.py [--gpus N --steps K --warmup W]
+Run: python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
+     A plain run sets up, warms up, times the K steps, checks that the decode
+     reproduced the lost shard, and prints the result line with the headline
+     figure (value, ms_per_step) and the encode / decode split its HIP events
+     give. Everything that takes runs of its own is behind --full: the oracle
+     digests, the matrix cross-check, the random-location, CRC, end-to-end and
+     host-call legs, the HBM probes and rooflines, the CPU baseline (the
+     paragraphs below; the --no-* options trim a --full run).
+     --dump-outputs DIR: after the timed steps, what the last step computed
+     (every stripe's parity rows and repaired row) goes to DIR/parity.npy and
+     DIR/decode.npy as float32: the whole array where it fits its share of
+     64 MB, else the bytes at a fixed seeded sample of positions (1-D, the
+     same positions in every run with the same arguments; the inputs are a
+     function of the arguments alone). With more than one rank each rank
+     writes its own stripes' share as <name>_rank<R>.npy.
      --gpus N > 1 without a launcher: bench.py starts
          python -m torch.distributed.run --nproc-per-node N bench.py ...
      as a child process before anything touches the GPU, relays its output and
@@ -25,7 +39,7 @@ The decode is timed through the decodeBulk boundary itself (hrs_decode_dev:
 the product's argument checks and decode-matrix cache lookup on every call);
 the matrix rank 0 broadcasts over RCCL is a cross-check only.
 
-After timing, every stripe's parity and decoded row get a SHA-256; rank 0
+With --full, after timing, every stripe's parity and decoded row get a SHA-256; rank 0
 gets every rank's per-stripe digests and hashes them per block of 256 global
 stripes (tools/stripe_digests.py), so any partition of the stripes over the
 ranks (weak or strong scaling) is compared with the C oracle's digests of the
@@ -84,6 +98,13 @@ def parse(argv=None):
     ap.add_argument("--force-dist", action="store_true",
                     help="create the process group even with one rank, so the collectives really run "
                          "(one-GPU rehearsal of the RCCL calls)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run every check and leg beside the headline figure "
+                         "(oracle digests, CRC / random-location / end-to-end / host-call legs, HBM probes, "
+                         "CPU baseline)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs to DIR/<name>.npy (float32; a fixed seeded sample "
+                         "of an output too large for its share of 64 MB)")
     ap.add_argument("--print-launch", action="store_true",
                     help="print the launch decision as JSON and exit (no GPU work; tests)")
     return ap.parse_args(argv)
@@ -842,6 +863,33 @@ def load_traffic(kernel, workload):
     return table[key], None
 
 
+DUMP_BYTES = 48 << 20  # --dump-outputs: float32 bytes over all files of all ranks (under the 64 MB it may take)
+
+
+def dump_outputs(path, outputs, rank, world):
+    """--dump-outputs: each (name, uint8 device tensor) of `outputs` to
+    path/<name>.npy as float32. The files share DUMP_BYTES in proportion to
+    their tensors' sizes (split evenly over the ranks); a tensor larger than
+    its share is sampled at sorted positions drawn once from a fixed seed, so
+    every run with the same arguments writes the same positions."""
+    os.makedirs(path, exist_ok=True)
+    total = sum(t.numel() for _, t in outputs)
+    budget = DUMP_BYTES // 4 // world
+    for i, (name, t) in enumerate(outputs):
+        share = budget * t.numel() // total
+        if t.numel() > share:
+            flat = np.sort(np.random.default_rng([0x5EED00D0, i]).integers(0, t.numel(), share))
+            t = t[tuple(torch.as_tensor(a, device=t.device) for a in np.unravel_index(flat, tuple(t.shape)))]
+        suffix = "" if world == 1 else f"_rank{rank}"
+        np.save(os.path.join(path, name + suffix + ".npy"), t.cpu().numpy().astype(np.float32))
+
+
+def close_dist():
+    if dist.is_available() and dist.is_initialized():
+        dist.barrier()
+        dist.destroy_process_group()
+
+
 def main():
     argv = sys.argv[1:]
     args = parse(argv)
@@ -877,22 +925,24 @@ def run(args):
     n = k + p
     dev = f"cuda:{local}"
     code = HipReedSolomonCode(k, p, device=local)
-    golden = load_golden()
-    # the config-5 leg's host-memory guard, decided before any large allocation
-    # and agreed over the ranks (every rank runs the leg with the same S, or none)
-    local_ranks = int(os.environ.get("LOCAL_WORLD_SIZE", "1"))
-    e2e_S, e2e_why = (0, "skipped: --no-e2e") if args.no_e2e else e2e_plan(host_available_bytes(), local_ranks)
-    e2e_S = parallel.min_over_ranks(e2e_S, dev)
-
-    # coding matrices: built on rank 0, broadcast over RCCL, checked everywhere
-    # (the timed decode goes through hrs_decode_dev; the broadcast D is the
-    # cross-check of its output below)
     erased = [p]  # data shard 0 = hops location p
     to_read = sorted(code.locationsToReadForDecode(erased))
     ntr = [x for x in range(n) if x not in to_read]
-    G = parallel.broadcast_matrix(code.encodeMatrix(), dev)
-    D = parallel.broadcast_matrix(code.decodeMatrix(erased, ntr), dev)
-    D_live = np.ascontiguousarray(D[:, to_read])
+    if args.full:
+        golden = load_golden()
+        # the config-5 leg's host-memory guard, decided before any large allocation
+        # and agreed over the ranks (every rank runs the leg with the same S, or none)
+        local_ranks = int(os.environ.get("LOCAL_WORLD_SIZE", "1"))
+        e2e_S, e2e_why = (0, "skipped: --no-e2e") if args.no_e2e else e2e_plan(host_available_bytes(), local_ranks)
+        e2e_S = parallel.min_over_ranks(e2e_S, dev)
+
+        # coding matrices: built on rank 0, broadcast over RCCL, checked everywhere
+        # (the timed decode goes through hrs_decode_dev; the broadcast D is the
+        # cross-check of its output below)
+        G = parallel.broadcast_matrix(code.encodeMatrix(), dev)
+        D = parallel.broadcast_matrix(code.decodeMatrix(erased, ntr), dev)
+        D_live = np.ascontiguousarray(D[:, to_read])
+        assert G.shape == (p, k)
 
     # synthetic stripes, resident in HBM before timing: [S, n, L] hops order;
     # data rows = splitmix64 keyed by (config 3, GLOBAL stripe index) with the
@@ -902,7 +952,6 @@ def run(args):
     synth.fill_data_rows(torch, stripes, 3, g0, k, p)
     out = torch.empty((S, len(erased), L), dtype=torch.uint8, device=dev)
     in_rows = [stripes[:, loc, :] for loc in to_read]
-    assert G.shape == (p, k)
 
     def step(ev=None):
         if ev is not None:
@@ -927,24 +976,62 @@ def run(args):
     wall = time.perf_counter() - t0
     parallel.barrier()
     elapsed = parallel.max_over_ranks(wall, dev)
-    dec_kernel = code.lastKernel()  # the decode step's kernel (decode_stripes ran last)
-    device.encode_stripes(code, stripes)  # idempotent: same parity; names the encode kernel
-    enc_kernel = code.lastKernel()
-    torch.cuda.synchronize()
+    if args.dump_outputs:  # what the last timed step left: every stripe's parity rows and repaired row
+        dump_outputs(args.dump_outputs, (("parity", stripes[:, :p]), ("decode", out)), rank, world)
 
     enc_all = [e[0].elapsed_time(e[1]) for e in events]
     dec_all = [e[1].elapsed_time(e[2]) for e in events]
     enc_ms = float(np.mean(enc_all))
     dec_ms = float(np.mean(dec_all))
+    # correctness of what was timed: the decode must reproduce data shard 0
+    ok = bool(torch.equal(out[:, 0], stripes[:, p]))
+    total_stripes = args.stripes if args.strong else S * world
+    user_bytes = 2 * k * L * total_stripes * args.steps
+    head = {
+        "metric": "RS encode+decode GiB/s device-resident; 1/2/4/8 MI355X; %HBM roofline",
+        "value": round(user_bytes / GiB / elapsed, 3),
+        "unit": "GiB/s",
+        "n_gpus": world,
+        "steps": args.steps,
+        "warmup": args.warmup,
+        "ms_per_step": round(elapsed * 1e3 / args.steps, 3),
+        "higher_is_better": True,
+        "scaling": "strong" if args.strong else "weak",
+        "vs_baseline": None,
+        "dtype": "u8",
+        "data": "synthetic: splitmix64 per global stripe (base seed 0x5EED0003), edge stripes "
+                "0x00/0xFF/ramp at global 0..2 (SURVEY §8d)",
+        "config": {
+            "workload": f"RS({k},{p}) encode + 1-erasure decode (data shard 0), {L >> 10} KiB cells, "
+                        f"{S} stripes/GPU, device-resident; encodeBulk / decodeBulk via hrs_encode_dev / "
+                        "hrs_decode_dev",
+            "stripes_per_gpu": S, "stripes_total": total_stripes, "cell_bytes": L, "k": k, "p": p,
+            "parallelism": f"stripe-sharded x{world} (RCCL: matrix broadcast + barriers only)",
+            "collectives": (dist.get_backend() if dist.is_available() and dist.is_initialized() else None),
+        },
+        "encode_GiBps_per_gpu": round(k * L * S / GiB / (enc_ms * 1e-3), 3),
+        "decode_GiBps_per_gpu": round(k * L * S / GiB / (dec_ms * 1e-3), 3),
+    }
+    if not args.full:
+        if not parallel.all_ok(ok, dev):
+            raise RuntimeError("benchmark output failed its round-trip check")
+        if rank == 0:
+            print(json.dumps(head), flush=True)
+        close_dist()
+        return 0
+
+    dec_kernel = code.lastKernel()  # the decode step's kernel (decode_stripes ran last)
+    device.encode_stripes(code, stripes)  # idempotent: same parity; names the encode kernel
+    enc_kernel = code.lastKernel()
+    torch.cuda.synchronize()
     # per-rank evidence for the scaling line: which rank or phase lagged
     per_rank = parallel.gather_objects({
         "rank": rank, "local_rank": local, "host": socket.gethostname(), "g0": g0, "stripes": S,
         "wall_s": round(wall, 6), "encode_ms": stats(enc_all), "decode_ms": stats(dec_all),
         "encode_kernel": traffic_key(enc_kernel), "decode_kernel": traffic_key(dec_kernel)})
 
-    # correctness of what was timed: the decode must reproduce data shard 0,
-    # and equal the broadcast matrix applied to the same survivors
-    ok = bool(torch.equal(out[:, 0], stripes[:, p]))
+    # further checks of what was timed: the data rows are still the synthetic
+    # ones, and the decode equals the broadcast matrix applied to the same survivors
     ok &= bool(torch.equal(stripes[min(S - 1, S // 2), p:].cpu(),
                            torch.from_numpy(synth.stripe_numpy(3, g0 + min(S - 1, S // 2), k, L))))
     xcheck = torch.empty_like(out)
@@ -1052,8 +1139,6 @@ def run(args):
         if e2e_set.get("bit_exact") is False:
             raise RuntimeError("config 5 device-set leg: outputs differ from the device-resident ones")
 
-    total_stripes = args.stripes if args.strong else S * world
-    user_bytes = 2 * k * L * total_stripes * args.steps
     enc_bytes = (k + p) * L * S  # algorithmic bytes per encode launch (read k, write p)
     dec_bytes = (k + len(erased)) * L * S
     enc_gbps = enc_bytes / (enc_ms * 1e-3) / 1e9
@@ -1070,30 +1155,8 @@ def run(args):
         rand_traffic, rand_traffic_why = load_traffic(batch_kernel, wl)
         dcrc_traffic, dcrc_traffic_why = load_traffic(dfused_kernel, wl)
         res = {
-            "metric": "RS encode+decode GiB/s device-resident; 1/2/4/8 MI355X; %HBM roofline",
-            "value": round(user_bytes / GiB / elapsed, 3),
-            "unit": "GiB/s",
-            "n_gpus": world,
-            "steps": args.steps,
-            "warmup": args.warmup,
-            "ms_per_step": round(elapsed * 1e3 / args.steps, 3),
-            "higher_is_better": True,
-            "scaling": "strong" if args.strong else "weak",
-            "vs_baseline": None,
-            "dtype": "u8",
-            "data": "synthetic: splitmix64 per global stripe (base seed 0x5EED0003), edge stripes "
-                    "0x00/0xFF/ramp at global 0..2 (SURVEY §8d)",
-            "config": {
-                "workload": f"RS({k},{p}) encode + 1-erasure decode (data shard 0), {L >> 10} KiB cells, "
-                            f"{S} stripes/GPU, device-resident; encodeBulk / decodeBulk via hrs_encode_dev / "
-                            "hrs_decode_dev",
-                "stripes_per_gpu": S, "stripes_total": total_stripes, "cell_bytes": L, "k": k, "p": p,
-                "parallelism": f"stripe-sharded x{world} (RCCL: matrix broadcast + barriers only)",
-                "collectives": (dist.get_backend() if dist.is_available() and dist.is_initialized() else None),
-            },
+            **head,
             "parity_vs_oracle": vs_oracle,
-            "encode_GiBps_per_gpu": round(k * L * S / GiB / (enc_ms * 1e-3), 3),
-            "decode_GiBps_per_gpu": round(k * L * S / GiB / (dec_ms * 1e-3), 3),
             "per_rank": per_rank,
             "roofline": {
                 "kernel": traffic_key(enc_kernel),
@@ -1171,9 +1234,7 @@ def run(args):
             res["cpu_baseline_1thread"] = cpu_baseline(k, p, L, 40, threads=1)
             res["cpu_baseline"]["gpu_vs_cpu"] = round(res["value"] / res["cpu_baseline"]["value"], 1)
         print(json.dumps(res), flush=True)
-    if dist.is_available() and dist.is_initialized():
-        dist.barrier()
-        dist.destroy_process_group()
+    close_dist()
     return 0
 
 

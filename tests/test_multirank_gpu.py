@@ -20,7 +20,8 @@ pytestmark = pytest.mark.gpu
 
 
 def bench_line(nproc, stripes, port, self_launch=False, strong=False):
-    common = ["--stripes", str(stripes), "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-e2e"]
+    common = ["--stripes", str(stripes), "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline",
+              "--no-e2e"]
     common += ["--strong"] if strong else []
     if nproc == 1:
         cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1"] + common
@@ -93,7 +94,7 @@ def test_rccl_collectives_single_rank(cuda):
     the N-rank curve is the driver's.)"""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_PORT")}
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--force-dist", "--dist-backend", "nccl",
-           "--stripes", "256", "--steps", "2", "--warmup", "1", "--no-cpu-baseline"]
+           "--stripes", "256", "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline"]
     out = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT, env=env)
     assert out.returncode == 0, out.stderr[-3000:]
     line = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("{")][-1])
