@@ -409,6 +409,58 @@ hrs_status hrs_decode_crc_dev(hrs_codec* codec, const uint8_t* const* rows, size
                               const int* not_to_read, int num_not_to_read, size_t len, size_t nstripes,
                               const uint32_t* crc_in, uint32_t* crc_out, void* stream);
 
+/* ---- stripe scrubbing: ReedSolomonCode.computeErrorLocations in bulk ----
+ * Whether a stripe at rest is still a codeword, and which cells went bad when
+ * nothing reported an erasure. For each byte column c of each stripe the
+ * column data[l] = rows[l][c], l in [0, n) in hops order, goes through
+ * computeErrorLocations (ReedSolomonCode.java:243-287, computeSyndrome
+ * :298-307) exactly as the Java runs it, its quirks included: the
+ * elimination's row-wise pivot search (GaloisField.java:412-451), no
+ * resolvable error at parity_size 1, resolved words with a wrong location set
+ * at larger parity sizes. A stripe's report aggregates its columns in
+ * HRS_SCRUB_HEAD + n uint32 words:
+ *   word 0 HRS_SCRUB_BAD         columns with a nonzero syndrome
+ *   word 1 HRS_SCRUB_UNRESOLVED  columns where the method returns false
+ *   word 2 HRS_SCRUB_FIRST_BAD   lowest column counted in word 0, or HRS_SCRUB_NONE
+ *   word 3                       reserved, 0
+ *   word 4 + l                   columns that returned true and whose errorLocations holds l
+ * Columns that return false add nothing to words 4... Every word is a count
+ * or a minimum: the report does not depend on scheduling. The locations with
+ * a nonzero count are the stripe's erasure list for hrs_decode_batch_dev.
+ * rs codes with parity_size <= 8 only (HRS_EINVAL otherwise). */
+#define HRS_SCRUB_BAD 0
+#define HRS_SCRUB_UNRESOLVED 1
+#define HRS_SCRUB_FIRST_BAD 2
+#define HRS_SCRUB_HEAD 4            /* words before the per-location counts */
+#define HRS_SCRUB_NONE 0xFFFFFFFFu
+
+/* ReedSolomonCode.computeErrorLocations on one column, host only (works on
+ * HRS_DEVICE_NONE handles). data[n] in [0,255], hops order; mutated as the
+ * Java mutates it (:281-285). locations has room for n, filled ascending;
+ * *resolved receives the method's boolean. */
+hrs_status hrs_compute_error_locations(const hrs_codec* codec, int* data, int* locations, int* num_locations,
+                                       int* resolved);
+
+/* Device-resident batch: rows[n] DEVICE pointers of stripe 0 (none NULL),
+ * stripe s at rows[l] + s * stride. reports: DEVICE uint32, stripe s at
+ * reports + s * report_stride (words, >= 4 + n); its 4 + n words are fully
+ * overwritten. 16-byte aligned rows and stride take the vector kernel over
+ * the whole 2 KiB windows; the row tail, or everything otherwise, a
+ * byte-granular kernel. len == 0 or nstripes == 0: nothing is touched.
+ * Asynchronous on stream. */
+hrs_status hrs_scrub_dev(hrs_codec* codec, const uint8_t* const* rows, size_t stride, size_t len, size_t nstripes,
+                         uint32_t* reports, size_t report_stride, void* stream);
+
+/* Same over a HOST batch laid out like hrs_decode_batch_host (stripe s holds
+ * location l at stripes + s * stripe_stride + l * row_stride); reports is a
+ * HOST array. Runtime-pinned stripes are read in place by one launch, any
+ * other memory is staged through the host-batch pipeline. Synchronous.
+ * The cells must not overlap (HRS_EINVAL): row_stride >= len, and with more
+ * than one stripe stripe_stride >= len and either a stripe's rows lie inside
+ * the stripe stride or a row's stripes inside the row stride. */
+hrs_status hrs_scrub_batch_host(hrs_codec* codec, const uint8_t* stripes, size_t row_stride, size_t stripe_stride,
+                                size_t len, size_t nstripes, uint32_t* reports, size_t report_stride);
+
 /* Kernel selection for tests and benchmarks: 0 = auto (default), 1 = force
  * the runtime-matrix bit-sliced kernel, 2 = force the byte-granular kernel,
  * 3 = auto, except that hrs_encode_crc_dev takes the fused kernel whenever the

@@ -242,6 +242,35 @@ class HipReedSolomonCode : public HipCode {
  public:
   HipReedSolomonCode(int stripeSize, int paritySize, int device = -1)
       : HipCode(HRS_CODE_RS, stripeSize, paritySize, device) {}
+
+  // ReedSolomonCode.computeErrorLocations(int[] data, Set<Integer> errorLocations)
+  // (ReedSolomonCode.java:243-287): data is mutated as the Java mutates it,
+  // errorLocations is cleared and filled (ascending). Host only.
+  bool computeErrorLocations(std::vector<int>& data, std::vector<int>& errorLocations) const {
+    if (static_cast<int>(data.size()) != stripeSize() + paritySize())
+      throw std::invalid_argument("computeErrorLocations: data must hold stripeSize + paritySize symbols");
+    errorLocations.assign(data.size(), 0);
+    int nloc = 0, resolved = 0;
+    check(hrs_compute_error_locations(h_, data.data(), errorLocations.data(), &nloc, &resolved), h_);
+    errorLocations.resize(nloc);
+    return resolved != 0;
+  }
+
+  // Stripe scrubbing (hrs_scrub_dev): computeErrorLocations over every byte
+  // column of nstripes device-resident stripes, one report of
+  // HRS_SCRUB_HEAD + n words per stripe (layout: hrs.h). Asynchronous on stream.
+  void scrubDev(const std::vector<const uint8_t*>& rows, size_t stride, size_t len, size_t nstripes,
+                uint32_t* reports, size_t reportStride, void* stream = nullptr) {
+    if (static_cast<int>(rows.size()) != stripeSize() + paritySize())
+      throw std::invalid_argument("scrubDev: row count does not match the codec");
+    check(hrs_scrub_dev(h_, rows.data(), stride, len, nstripes, reports, reportStride, stream), h_);
+  }
+
+  // The same over a host batch (hrs_scrub_batch_host); reports is a host array.
+  void scrubBatchHost(const uint8_t* stripes, size_t rowStride, size_t stripeStride, size_t len, size_t nstripes,
+                      uint32_t* reports, size_t reportStride) {
+    check(hrs_scrub_batch_host(h_, stripes, rowStride, stripeStride, len, nstripes, reports, reportStride), h_);
+  }
 };
 
 class HipXORCode : public HipCode {

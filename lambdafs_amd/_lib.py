@@ -43,6 +43,7 @@ EXPORTS = (
     "hrs_set_kernel_mode", "hrs_last_kernel", "hrs_wait", "hrs_release",
     "hrs_device_count", "hrs_codec_device", "hrs_decode_batch_host_multi", "hrs_encode_batch_host_multi",
     "hrs_set_timing", "hrs_ticket_gpu_ms", "hrs_last_host_path",
+    "hrs_compute_error_locations", "hrs_scrub_dev", "hrs_scrub_batch_host",
 )
 # include/hrs_probe.h, exported by libhrs_probe.so
 PROBE_EXPORTS = ("hrs_probe_stream", "hrs_probe_rows")
@@ -122,6 +123,9 @@ def lib():
         "hrs_set_kernel_mode": ([P, I], I),
         "hrs_last_kernel": ([P], ctypes.c_char_p),
         "hrs_last_host_path": ([P], ctypes.c_char_p),
+        "hrs_compute_error_locations": ([P, IP, IP, IP, IP], I),
+        "hrs_scrub_dev": ([P, PP, S, S, S, P, S, P], I),
+        "hrs_scrub_batch_host": ([P, P, S, S, S, S, P, S], I),
     }
     for name, (args, res) in sigs.items():
         f = getattr(L, name)

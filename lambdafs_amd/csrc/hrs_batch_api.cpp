@@ -373,7 +373,8 @@ std::vector<RowRun> runs_of(const int* locs, int nlocs) {  // locs ascending
 // dout)` queues the kernels on the slot's stream, `writes(i)` = how many
 // output rows stripe s0 + i has (rows 0.. of its output block). Host
 // stripe s: rows at hin + s * in_stripe + l * in_row; outputs at
-// hout + s * out_stripe + t * out_row.
+// hout + s * out_stripe + t * out_row. out_rows_max may be 0 (the scrub
+// reads only): no output block, nothing copied back.
 template <typename Reads, typename Compute, typename Writes>
 hrs_status host_batch(hrs_codec* c, const uint8_t* hin, size_t in_row, size_t in_stripe, int img_rows, uint8_t* hout,
                       size_t out_row, size_t out_stripe, int out_rows_max, size_t len, size_t nstripes, Reads reads,
@@ -383,8 +384,10 @@ hrs_status host_batch(hrs_codec* c, const uint8_t* hin, size_t in_row, size_t in
   const size_t out_stripe_dev = dpitch * static_cast<size_t>(out_rows_max);
   size_t chunk = std::max<size_t>(1, hbatch_target_bytes() / std::max<size_t>(1, img_stripe));
   chunk = std::min(chunk, nstripes);
+  // out_rows_max == 0: a read-only job (the scrub), hout is not touched
   const bool pinned = runtime_pinned(hin, batch_span(nstripes, in_stripe, img_rows, in_row, len)) &&
-                      runtime_pinned(hout, batch_span(nstripes, out_stripe, out_rows_max, out_row, len));
+                      (out_rows_max == 0 ||
+                       runtime_pinned(hout, batch_span(nstripes, out_stripe, out_rows_max, out_row, len)));
   const size_t dev_bytes = chunk * (img_stripe + out_stripe_dev);
   const size_t pin_bytes = pinned ? 0 : dev_bytes;  // staging mirrors the device image
   // pageable callers, zero copy: the kernels read each chunk's image from the
@@ -748,9 +751,94 @@ hrs_status encode_batch_host_impl(hrs_codec* c, uint8_t* stripes, size_t row_str
                                     p, len, nstripes, reads, compute, writes));
 }
 
+// hrs_scrub_batch_host: every stripe's n rows are its reads, there are no
+// output rows; the reports accumulate in the handle's device buffer (dense,
+// 4 + n words per stripe) and come back in one copy.
+hrs_status scrub_batch_host_impl(hrs_codec* c, const uint8_t* stripes, size_t row_stride, size_t stripe_stride,
+                                 size_t len, size_t nstripes, uint32_t* reports, size_t report_stride) {
+  DeviceGuard g(c->device);
+  if (!g.ok) return fail(c, HRS_EDEVICE, "cannot select HIP device %d", c->device);
+  const int n = c->n;
+  const size_t nwords = static_cast<size_t>(hrs::kScrubHead + n);
+  const size_t bytes = nstripes * nwords * sizeof(uint32_t);
+  if (c->scrub_reports_bytes < bytes) {  // every earlier batch has completed: the calls are synchronous
+    if (c->scrub_reports) (void)hipFree(c->scrub_reports);
+    c->scrub_reports = nullptr;
+    c->scrub_reports_bytes = 0;
+    const hipError_t e = hipMalloc(&c->scrub_reports, bytes);
+    if (e != hipSuccess) return fail(c, HRS_ENOMEM, "hipMalloc(%zu): %s", bytes, hipGetErrorString(e));
+    c->scrub_reports_bytes = bytes;
+  }
+  uint32_t* drep = c->scrub_reports;
+  std::vector<const uint8_t*> rows(n);
+  hrs_status st = hbatch_slot(c, 0, 0, 0);
+  if (st != HRS_OK) return st;
+  uint8_t* zs = nullptr;
+  if (zero_copy_on() && host_device_ptr(stripes, batch_span(nstripes, stripe_stride, n, row_stride, len), &zs)) {
+    // runtime-pinned: one launch reads the caller's stripes across the host link
+    const hipStream_t hs = c->hbatch[0].stream;
+    for (int l = 0; l < n; ++l) rows[l] = zs + static_cast<size_t>(l) * row_stride;
+    {
+      hrs::GridCap cap(zero_copy_blocks());
+      st = run_scrub(c, rows.data(), stripe_stride, len, nstripes, drep, nwords, hs);
+    }
+    if (st == HRS_OK) {
+      const hipError_t e = hipStreamSynchronize(hs);
+      if (e != hipSuccess) st = hip_fail(c, e, "hipStreamSynchronize");
+    }
+  } else {
+    const std::vector<RowRun> all_rows{{0, n}};
+    auto reads = [&](size_t) -> const std::vector<RowRun>& { return all_rows; };
+    auto writes = [&](size_t) -> int { return 0; };
+    auto compute = [&](hipStream_t hs, size_t s0, size_t ns, uint8_t* dimg, size_t img_stripe, size_t dpitch, uint8_t*,
+                       size_t) -> hrs_status {
+      for (int l = 0; l < n; ++l) rows[l] = dimg + static_cast<size_t>(l) * dpitch;
+      return run_scrub(c, rows.data(), img_stripe, len, ns, drep + s0 * nwords, nwords, hs);
+    };
+    st = host_batch(c, stripes, row_stride, stripe_stride, n, const_cast<uint8_t*>(stripes), row_stride,
+                    stripe_stride, 0, len, nstripes, reads, compute, writes);
+  }
+  st = drain_hbatch(c, st);
+  if (st != HRS_OK) return st;
+  std::vector<uint32_t> host(nstripes * nwords);
+  const hipError_t e = hipMemcpy(host.data(), drep, bytes, hipMemcpyDeviceToHost);
+  if (e != hipSuccess) return hip_fail(c, e, "hipMemcpy reports");
+  for (size_t s = 0; s < nstripes; ++s)
+    std::memcpy(reports + s * report_stride, host.data() + s * nwords, nwords * sizeof(uint32_t));
+  return HRS_OK;
+}
+
 }  // namespace
 
 extern "C" {
+
+hrs_status hrs_scrub_batch_host(hrs_codec* c, const uint8_t* stripes, size_t row_stride, size_t stripe_stride,
+                                size_t len, size_t nstripes, uint32_t* reports, size_t report_stride) {
+  if (!c) return HRS_EINVAL;
+  hrs_status st = scrub_code_ok(c, report_stride, true);
+  if (st != HRS_OK) return st;
+  if (!stripes || !reports) return fail(c, HRS_EINVAL, "stripes or reports is NULL");
+  if (nstripes > 0x7fffffffu) return fail(c, HRS_EINVAL, "too many stripes");
+  if (len > 0xffffffffu) return fail(c, HRS_EINVAL, "rows of %zu bytes: column indices are 32-bit", len);
+  if (nstripes == 0 || len == 0) return HRS_OK;
+  // A read-only pass over a mis-strided batch would report "clean" or "bad"
+  // with no error: the cells must not overlap. Rows of a stripe packed inside
+  // the stripe stride, or stripes of a row packed inside the row stride.
+  const size_t rows_span = static_cast<size_t>(c->n - 1) * row_stride + len;
+  const size_t stripes_span = (nstripes - 1) * stripe_stride + len;
+  const bool stripes_apart =
+      nstripes == 1 || (stripe_stride >= len && (stripe_stride >= rows_span || row_stride >= stripes_span));
+  if (row_stride < len || !stripes_apart)
+    return fail(c, HRS_EINVAL, "cells overlap: row_stride %zu, stripe_stride %zu, len %zu, %d rows, %zu stripes",
+                row_stride, stripe_stride, len, c->n, nstripes);
+  st = scrub_batch_host_impl(c, stripes, row_stride, stripe_stride, len, nstripes, reports, report_stride);
+  if (st == HRS_OK) {
+    DeviceGuard g(c->device);
+    c->last_host_path =
+        batch_path(g.ok && runtime_pinned(stripes, batch_span(nstripes, stripe_stride, c->n, row_stride, len)));
+  }
+  return st;
+}
 
 hrs_status hrs_decode_batch_dev(hrs_codec* c, const uint8_t* stripes, size_t row_stride, size_t stripe_stride,
                                 const int* erased, int max_erased, uint8_t* out, size_t out_row_stride,

@@ -103,6 +103,10 @@ struct hrs_codec {
     hipEvent_t in_done = nullptr;
     hipEvent_t comp_done = nullptr;
   } hbatch[hrs::kHostBatchSlots];
+  // hrs_scrub_batch_host: the reports accumulate here (device) and come back
+  // in one copy when the batch has run
+  uint32_t* scrub_reports = nullptr;
+  size_t scrub_reports_bytes = 0;
   hipStream_t hbatch_in = nullptr;   // H2D of every host-batch slot
   hipStream_t hbatch_out = nullptr;  // D2H of every host-batch slot
   // asynchronous host-buffer calls (hrs_*_submit / hrs_collect): a ring of
@@ -233,6 +237,15 @@ hrs_status apply_crc_impl(hrs_codec* c, const uint8_t* m, int nout, int nin, con
 // would read the cells across the link a second time).
 bool encode_crc_one_pass(const hrs_codec* c, size_t len, size_t nstripes);
 bool apply_crc_one_pass(const hrs_codec* c, int nout, int nlive, size_t len);
+
+// ---- stripe scrubbing (hrs_scrub_api.cpp)
+// The code and report_stride checks of the scrub entry points (rs only,
+// p <= 8, report_stride >= 4 + n when with_reports).
+hrs_status scrub_code_ok(hrs_codec* c, size_t report_stride, bool with_reports);
+// Empty reports, then the vector kernel over the whole 2 KiB windows and the
+// byte-granular kernel over the rest, all on stream s. rows[n]: none NULL.
+hrs_status run_scrub(hrs_codec* c, const uint8_t* const* rows, size_t stride, size_t len, size_t nstripes,
+                     uint32_t* reports, size_t report_stride, hipStream_t s);
 
 }  // namespace hrs::api
 #pragma GCC visibility pop

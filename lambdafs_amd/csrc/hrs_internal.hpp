@@ -95,6 +95,32 @@ struct BatchArgs {
 
 hipError_t launch_batch_bitsliced(const BatchArgs& a, int max_nout, int max_nin, hipStream_t s);
 
+// ---- stripe scrubbing (hrs_scrub.hip): computeErrorLocations over every column
+
+constexpr int kScrubHead = 4;               // report words before the per-location counts (HRS_SCRUB_HEAD)
+constexpr uint32_t kScrubNone = 0xFFFFFFFFu;  // first-bad-column word of a clean stripe (HRS_SCRUB_NONE)
+constexpr int kScrubMaxRows = 255;          // hrs_create admits n = k + p <= 255 (ReedSolomonCode.java:57)
+
+struct ScrubArgs {
+  const uint8_t* rows[kScrubMaxRows];  // location l of stripe s at rows[l] + s * stride
+  uint64_t stride;
+  uint64_t len;                        // bytes per row
+  uint64_t col0;                       // bytewise: first column covered (tails: nwin * 2048)
+  uint64_t nwin;                       // vector: full 2 KiB windows per row
+  uint64_t ntasks;                     // vector: nstripes * nwin; bytewise: nstripes * (len - col0)
+  uint32_t* reports;                   // stripe s at reports + s * report_stride (words)
+  uint64_t report_stride;
+  int n, p;
+  int order;                           // window -> wave order (task_order), set at launch
+  int pad_;
+};
+
+// Writes the empty report (zeros, kScrubNone in word 2) of every stripe; the
+// two kernels then add into it.
+hipError_t launch_scrub_init(uint32_t* reports, uint64_t report_stride, int n, uint64_t nstripes, hipStream_t s);
+hipError_t launch_scrub(const ScrubArgs& a, hipStream_t s);
+hipError_t launch_scrub_bytewise(const ScrubArgs& a, hipStream_t s);
+
 // ---- stream gates of the queued host pipeline (hrs_gate.hip)
 // gate: waits until *ready (a coherent pinned word the host writes) reaches
 // `want` (serial-number order), or `timeout` wall-clock ticks pass (then *fail

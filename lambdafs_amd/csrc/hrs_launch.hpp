@@ -65,6 +65,7 @@ constexpr int kOrderBatch = 1;         // heterogeneous repair batches
 constexpr int kOrderFusedEncode = 1;   // encode + CRC-32
 constexpr int kOrderDecodeCrc = 1;     // repair + CRC-32
 constexpr int kOrderCrc = 1;           // CRC-32 windows
+constexpr int kOrderScrub = 1;         // scrub windows (not swept: the encode's order)
 
 template <class A>
 inline A with_order(A a, int dflt) {

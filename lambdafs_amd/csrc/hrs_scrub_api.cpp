@@ -1,0 +1,136 @@
+// Stripe scrubbing behind the C ABI: the scalar computeErrorLocations on the
+// host (hrs_compute_error_locations, host-only handles included) and the
+// device-resident batch (hrs_scrub_dev). The host-memory batch is in
+// hrs_batch_api.cpp beside the pipeline it shares. The per-column algorithm
+// is hrs_locator.hpp, the same code the kernels of hrs_scrub.hip run.
+#include <hip/hip_runtime.h>
+
+#include "../../include/hrs.h"
+#include "gf256.hpp"
+#include "hrs_codec.hpp"
+#include "hrs_internal.hpp"
+#include "hrs_locator.hpp"
+
+namespace hrs::api {
+
+namespace {
+
+constexpr hrs::gf::Tables kHostTables = hrs::gf::make_tables();
+
+template <int P>
+void column_syndromes(const hrs::locator::Field& f, int n, const int* data, uint8_t* out) {
+  uint8_t s[P] = {};
+  for (int l = n - 1; l >= 0; --l) hrs::locator::horner_step<P>(f, s, static_cast<uint8_t>(data[l]));
+  for (int i = 0; i < P; ++i) out[i] = s[i];
+}
+
+}  // namespace
+
+hrs_status scrub_code_ok(hrs_codec* c, size_t report_stride, bool with_reports) {
+  if (c->kind != HRS_CODE_RS) return fail(c, HRS_EINVAL, "error location is defined for the rs code only");
+  if (c->p > hrs::locator::kMaxSyndromes)
+    return fail(c, HRS_EINVAL, "error location supports parity_size <= %d, this codec has %d",
+                hrs::locator::kMaxSyndromes, c->p);
+  if (c->n > hrs::kScrubMaxRows)  // hrs_create admits no such handle; ScrubArgs and the LDS histogram hold this many
+    return fail(c, HRS_EINVAL, "scrubbing supports at most %d locations, this codec has %d", hrs::kScrubMaxRows, c->n);
+  if (with_reports && report_stride < static_cast<size_t>(hrs::kScrubHead + c->n))
+    return fail(c, HRS_EINVAL, "report_stride %zu is below 4 + n = %d words", report_stride, hrs::kScrubHead + c->n);
+  return HRS_OK;
+}
+
+hrs_status run_scrub(hrs_codec* c, const uint8_t* const* rows, size_t stride, size_t len, size_t nstripes,
+                     uint32_t* reports, size_t report_stride, hipStream_t s) {
+  hipError_t e = hrs::launch_scrub_init(reports, report_stride, c->n, nstripes, s);
+  if (e != hipSuccess) return hip_fail(c, e, "scrub init launch");
+  hrs::ScrubArgs a{};
+  bool vec_ok = stride % 16 == 0 && c->kernel_mode != 2;
+  for (int l = 0; l < c->n; ++l) {
+    a.rows[l] = rows[l];
+    vec_ok &= aligned16(rows[l]);
+  }
+  a.stride = stride;
+  a.len = len;
+  a.reports = reports;
+  a.report_stride = report_stride;
+  a.n = c->n;
+  a.p = c->p;
+  a.nwin = vec_ok ? len / hrs::kWindowBytes : 0;
+  if (a.nwin > 0) {
+    a.ntasks = a.nwin * nstripes;
+    e = hrs::launch_scrub(a, s);
+    if (e != hipSuccess) return hip_fail(c, e, "scrub launch");
+    c->last_kernel = hrs::last_kernel();
+  }
+  a.col0 = a.nwin * hrs::kWindowBytes;
+  if (a.col0 < len) {
+    a.ntasks = (len - a.col0) * nstripes;
+    e = hrs::launch_scrub_bytewise(a, s);
+    if (e != hipSuccess) return hip_fail(c, e, "scrub bytewise launch");
+    if (a.nwin == 0) c->last_kernel = hrs::last_kernel();
+  }
+  return HRS_OK;
+}
+
+}  // namespace hrs::api
+
+using namespace hrs::api;
+
+extern "C" {
+
+hrs_status hrs_compute_error_locations(const hrs_codec* cc, int* data, int* locations, int* num_locations,
+                                       int* resolved) {
+  auto* c = const_cast<hrs_codec*>(cc);
+  if (!c) return HRS_EINVAL;
+  if (!data || !locations || !num_locations || !resolved)
+    return fail(c, HRS_EINVAL, "computeErrorLocations: an argument is NULL");
+  hrs_status st = scrub_code_ok(c, 0, false);
+  if (st != HRS_OK) return st;
+  for (int l = 0; l < c->n; ++l)
+    if (data[l] < 0 || data[l] > 255) return fail(c, HRS_EINVAL, "data[%d] = %d is outside [0, 255]", l, data[l]);
+  const hrs::locator::Field f{kHostTables.exp, kHostTables.log};
+  uint8_t s[hrs::locator::kMaxSyndromes] = {};
+  switch (c->p) {
+    case 1: column_syndromes<1>(f, c->n, data, s); break;
+    case 2: column_syndromes<2>(f, c->n, data, s); break;
+    case 3: column_syndromes<3>(f, c->n, data, s); break;
+    case 4: column_syndromes<4>(f, c->n, data, s); break;
+    case 5: column_syndromes<5>(f, c->n, data, s); break;
+    case 6: column_syndromes<6>(f, c->n, data, s); break;
+    case 7: column_syndromes<7>(f, c->n, data, s); break;
+    default: column_syndromes<8>(f, c->n, data, s); break;
+  }
+  *num_locations = 0;
+  bool clean = true;
+  for (int i = 0; i < c->p; ++i) clean &= s[i] == 0;
+  if (clean) {
+    *resolved = 1;
+    return HRS_OK;
+  }
+  int nloc = 0;
+  uint8_t loc[hrs::locator::kMaxErrors], err[hrs::locator::kMaxErrors];
+  *resolved = hrs::locator::locate(f, c->n, c->p, s, &nloc, loc, err) ? 1 : 0;
+  for (int j = 0; j < nloc; ++j) {  // ReedSolomonCode.java:281-285: the decoded values are written back
+    locations[j] = loc[j];
+    data[loc[j]] ^= err[j];
+  }
+  *num_locations = nloc;
+  return HRS_OK;
+}
+
+hrs_status hrs_scrub_dev(hrs_codec* c, const uint8_t* const* rows, size_t stride, size_t len, size_t nstripes,
+                         uint32_t* reports, size_t report_stride, void* stream) {
+  if (!c) return HRS_EINVAL;
+  hrs_status st = scrub_code_ok(c, report_stride, true);
+  if (st != HRS_OK) return st;
+  if (!rows || !reports) return fail(c, HRS_EINVAL, "rows or reports is NULL");
+  for (int l = 0; l < c->n; ++l)
+    if (!rows[l]) return fail(c, HRS_EINVAL, "row %d is NULL", l);
+  if (nstripes > 0x7fffffffu) return fail(c, HRS_EINVAL, "too many stripes");
+  if (len > 0xffffffffu) return fail(c, HRS_EINVAL, "rows of %zu bytes: column indices are 32-bit", len);
+  if (len == 0 || nstripes == 0) return HRS_OK;
+  DeviceGuard g(c->device);
+  if (!g.ok) return fail(c, HRS_EDEVICE, "cannot select HIP device %d", c->device);
+  return run_scrub(c, rows, stride, len, nstripes, reports, report_stride, static_cast<hipStream_t>(stream));
+}
+
+}  // extern "C"

@@ -280,6 +280,79 @@ def crc32_rows(code, row_views, crc_in=None):
     return out
 
 
+SCRUB_BAD, SCRUB_UNRESOLVED, SCRUB_FIRST_BAD, SCRUB_HEAD = 0, 1, 2, 4  # report words (include/hrs.h)
+SCRUB_NONE = 0xFFFFFFFF
+
+
+def _scrub(code, rows, stride, L, S, ref):
+    torch = _lib.torch
+    n = code.stripeSize() + code.paritySize()
+    reports = torch.empty((S, SCRUB_HEAD + n), dtype=torch.int32, device=ref.device)
+    code._check(_lib.lib().hrs_scrub_dev(code._handle(), rows, stride, L, S, reports.data_ptr(), SCRUB_HEAD + n,
+                                         _stream(ref)))
+    return reports
+
+
+def scrub_stripes(code, stripes):
+    """computeErrorLocations over every byte column of every stripe of
+    stripes[S, n, L] (hrs_scrub_dev): an int32 tensor [S, 4 + n] holding the
+    uint32 report words of each stripe — bad columns, unresolved columns,
+    first bad column (SCRUB_NONE if clean), 0, then per location the columns
+    that resolved and blamed it."""
+    n = code.stripeSize() + code.paritySize()
+    if stripes.dim() != 3 or stripes.shape[1] != n:
+        raise ValueError(f"stripes must be [S, {n}, L]")
+    rows, stride, L, S = _stripe_rows(stripes, range(n))
+    return _scrub(code, rows, stride, L, S, stripes)
+
+
+def scrub_rows(code, row_views):
+    """scrub_stripes with explicit [S, L] row views, one per location in hops order."""
+    n = code.stripeSize() + code.paritySize()
+    if len(row_views) != n or any(v is None for v in row_views):
+        raise ValueError(f"need {n} row views")
+    rows, stride, L, S = _rows(row_views)
+    return _scrub(code, rows, stride, L, S, row_views[0])
+
+
+def scrub_batch_host(code, stripes):
+    """hrs_scrub_batch_host: scrub_stripes for stripes[S, n, L] in HOST memory
+    (numpy array or CPU tensor; pinned ones are read in place): a numpy uint32
+    array [S, 4 + n]."""
+    n = code.stripeSize() + code.paritySize()
+    sp, sshape, sstr = _host_ptr(stripes, "stripes")
+    if len(sshape) != 3 or sshape[1] != n or sstr[2] != 1:
+        raise ValueError(f"stripes must be [S, {n}, L] with unit byte stride")
+    S, L = sshape[0], sshape[2]
+    reports = np.zeros((S, SCRUB_HEAD + n), dtype=np.uint32)
+    code._check(_lib.lib().hrs_scrub_batch_host(code._handle(), sp, sstr[1], sstr[0], L, S, reports.ctypes.data,
+                                                SCRUB_HEAD + n))
+    return reports
+
+
+def scrub_to_erased(reports, p):
+    """The int32 [S, p] erasure array decode_batch takes from scrub reports
+    [S, 4 + n]: per stripe the locations with a nonzero count, ascending, -1
+    padded. ValueError for a stripe with unresolved columns or more than p
+    blamed locations (not repairable from the report alone)."""
+    torch = _lib.torch
+    if torch is not None and isinstance(reports, torch.Tensor):
+        reports = reports.cpu().numpy()
+    r = np.asarray(reports)
+    if r.ndim != 2 or r.shape[1] <= SCRUB_HEAD:
+        raise ValueError("reports must be [S, 4 + n]")
+    r = r.astype(np.int64) & 0xFFFFFFFF
+    erased = np.full((r.shape[0], int(p)), -1, dtype=np.int32)
+    for s in range(r.shape[0]):
+        if r[s, SCRUB_UNRESOLVED]:
+            raise ValueError(f"stripe {s}: {int(r[s, SCRUB_UNRESOLVED])} unresolved columns")
+        locs = np.flatnonzero(r[s, SCRUB_HEAD:])
+        if len(locs) > p:
+            raise ValueError(f"stripe {s}: {len(locs)} blamed locations, the code repairs {int(p)}")
+        erased[s, : len(locs)] = locs
+    return erased
+
+
 PROBE_COPY, PROBE_READ, PROBE_WRITE = 0, 1, 2
 WAVE_TASKS, GRID_STRIDE, BLOCK_RANGE = 0, 1, 2  # hrs_probe_stream schedules
 

@@ -571,6 +571,26 @@ class HipReedSolomonCode(_HipErasureCode):
             if erasedLocations[i] in decoded:
                 erasedValues[i] = int(outs[i][0])
 
+    def computeErrorLocations(self, data, errorLocations):
+        """ReedSolomonCode.computeErrorLocations(int[] data, Set<Integer>
+        errorLocations) (ReedSolomonCode.java:243-287): the locations of up to
+        paritySize / 2 corrupted symbols of one column [parity..., data...].
+        Mutates data as the Java does (:281-285), clears and fills the set,
+        returns the method's boolean. Host only (hrs_compute_error_locations):
+        works on a host-only handle; the bulk form is device.scrub_stripes."""
+        n = self._k + self._p
+        if len(data) != n:
+            raise ValueError(f"data must hold {n} symbols")
+        d = int_array(data)
+        locs = (ctypes.c_int * n)()
+        nloc, resolved = ctypes.c_int(0), ctypes.c_int(0)
+        self._check(_lib.lib().hrs_compute_error_locations(self._handle(), d, locs, ctypes.byref(nloc),
+                                                           ctypes.byref(resolved)))
+        data[:] = list(d)[:n]
+        errorLocations.clear()
+        errorLocations.update(locs[: nloc.value])
+        return bool(resolved.value)
+
 
 
 class HipXORCode(_HipErasureCode):
