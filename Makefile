@@ -20,7 +20,7 @@ API_OBJ  := $(patsubst %,build/%.o,$(API_SRC))
 
 JNI      := lambdafs_amd/libhrs_jni.so
 HARNESS  := tests/cpp/codec_harness tests/cpp/crc_model tests/cpp/jni_harness tests/cpp/host_logic tests/cpp/crc_tables \
-            tests/cpp/copy_pool_test tests/cpp/scrub_logic
+            tests/cpp/copy_pool_test tests/cpp/scrub_logic tests/cpp/heal_logic
 
 TOOLS    := tools/host_call_rate tools/host_pipeline_sweep tools/host_copy_probe
 
@@ -123,6 +123,11 @@ tests/cpp/scrub_logic: tests/cpp/scrub_logic.cpp include/hrs.h $(LIB) $(ORACLE)
 	g++ -O2 -std=c++17 -Wall -Iinclude -Ioracle -o $@ $< -Llambdafs_amd -lhrs -Loracle -loracle \
 	    -Wl,-rpath,'$$ORIGIN/../../lambdafs_amd' -Wl,-rpath,'$$ORIGIN/../../oracle'
 
+# Stripe healing on the CPU (hrs_heal_host) vs the oracle's post-call data, under the heal rule.
+tests/cpp/heal_logic: tests/cpp/heal_logic.cpp include/hrs.h $(LIB) $(ORACLE)
+	g++ -O2 -std=c++17 -Wall -Iinclude -Ioracle -o $@ $< -Llambdafs_amd -lhrs -Loracle -loracle \
+	    -Wl,-rpath,'$$ORIGIN/../../lambdafs_amd' -Wl,-rpath,'$$ORIGIN/../../oracle'
+
 # The CRC tables the kernels load, dumped for tests/test_crc_tables.py (host code;
 # hipcc only for the HIP headers hrs_crc.hpp includes).
 tests/cpp/crc_tables: tests/cpp/crc_tables.cpp lambdafs_amd/csrc/crc32.hpp lambdafs_amd/csrc/hrs_crc.hpp
@@ -145,7 +150,8 @@ CLANG    := /opt/rocm/lib/llvm/bin/clang
 SAN      := -fsanitize=address,undefined -fno-sanitize-recover=undefined -fno-omit-frame-pointer -g -O1
 HSAN     := -Xarch_host -fsanitize=address -Xarch_host -fsanitize=undefined -Xarch_host -fno-sanitize-recover=undefined \
             -Xarch_host -fno-omit-frame-pointer
-ASAN_BIN := $(ASAN_DIR)/host_logic $(ASAN_DIR)/jni_harness $(ASAN_DIR)/codec_harness $(ASAN_DIR)/scrub_logic
+ASAN_BIN := $(ASAN_DIR)/host_logic $(ASAN_DIR)/jni_harness $(ASAN_DIR)/codec_harness $(ASAN_DIR)/scrub_logic \
+            $(ASAN_DIR)/heal_logic
 ASAN_LOG := profiles/r06/asan
 
 ASAN_API := $(patsubst %,$(ASAN_DIR)/%.o,$(API_SRC))
@@ -170,6 +176,9 @@ $(ASAN_DIR)/host_logic: tests/cpp/host_logic.cpp $(ASAN_DIR)/libhrs.so $(ASAN_DI
 $(ASAN_DIR)/scrub_logic: tests/cpp/scrub_logic.cpp $(ASAN_DIR)/libhrs.so $(ASAN_DIR)/liboracle.so
 	$(CLANG)++ $(SAN) -std=c++17 -Iinclude -Ioracle -o $@ $< -L$(ASAN_DIR) -lhrs -loracle $(ASAN_RPATH)
 
+$(ASAN_DIR)/heal_logic: tests/cpp/heal_logic.cpp $(ASAN_DIR)/libhrs.so $(ASAN_DIR)/liboracle.so
+	$(CLANG)++ $(SAN) -std=c++17 -Iinclude -Ioracle -o $@ $< -L$(ASAN_DIR) -lhrs -loracle $(ASAN_RPATH)
+
 $(ASAN_DIR)/jni_harness: tests/cpp/jni_harness.c $(ASAN_DIR)/libhrs_jni.so $(ASAN_DIR)/liboracle.so
 	$(CLANG) $(SAN) -std=c11 -Iinclude -Ioracle -o $@ $< -L$(ASAN_DIR) -lhrs_jni -lhrs -loracle -lz -ldl $(ASAN_RPATH)
 
@@ -183,6 +192,7 @@ asan: $(ASAN_BIN)
 	  set -e; \
 	  $(ASAN_DIR)/host_logic; \
 	  $(ASAN_DIR)/scrub_logic; \
+	  $(ASAN_DIR)/heal_logic; \
 	  $(ASAN_DIR)/jni_harness --cpu; \
 	  for kp in "10 4" "12 4" "6 3" "3 2"; do $(ASAN_DIR)/codec_harness --host-only $$kp; done' \
 	  > $(ASAN_LOG)/asan_run.log 2>&1 || { cat $(ASAN_LOG)/asan_run.log; exit 1; }

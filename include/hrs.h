@@ -422,7 +422,7 @@ hrs_status hrs_decode_crc_dev(hrs_codec* codec, const uint8_t* const* rows, size
  *   word 0 HRS_SCRUB_BAD         columns with a nonzero syndrome
  *   word 1 HRS_SCRUB_UNRESOLVED  columns where the method returns false
  *   word 2 HRS_SCRUB_FIRST_BAD   lowest column counted in word 0, or HRS_SCRUB_NONE
- *   word 3                       reserved, 0
+ *   word 3                       0 (hrs_heal_*: HRS_SCRUB_PATCHED, below)
  *   word 4 + l                   columns that returned true and whose errorLocations holds l
  * Columns that return false add nothing to words 4... Every word is a count
  * or a minimum: the report does not depend on scheduling. The locations with
@@ -460,6 +460,49 @@ hrs_status hrs_scrub_dev(hrs_codec* codec, const uint8_t* const* rows, size_t st
  * the stripe stride or a row's stripes inside the row stride. */
 hrs_status hrs_scrub_batch_host(hrs_codec* codec, const uint8_t* stripes, size_t row_stride, size_t stripe_stride,
                                 size_t len, size_t nstripes, uint32_t* reports, size_t report_stride);
+
+/* ---- stripe healing: the scrub plus the write-back, in one pass ----
+ * The scalar method patches the column it located (data[loc] = decoded value,
+ * ReedSolomonCode.java:281-285); the scrub computes those values and drops
+ * them. Heal stores them, under this rule:
+ *   - a column for which computeErrorLocations returns true with a non-empty
+ *     location set is rewritten to the Java's post-call data; only the bytes
+ *     whose error value is nonzero are stored (a blamed location whose value
+ *     stands is counted in word 4 + l and not written);
+ *   - a column for which it returns false is left exactly as it was, also
+ *     where the Java wrote into it before returning false.
+ * The report is the scrub's report of the stripes as they were BEFORE the
+ * call, except
+ *   word 3 HRS_SCRUB_PATCHED     bytes this call stored = bytes that differ
+ *                                before and after (hrs_scrub_* keep writing 0)
+ * A resolved column with at most parity_size / 2 wrong bytes is always
+ * restored to the codeword it came from; beyond that the method usually
+ * returns false, and rarely resolves to another codeword (the code's distance
+ * limit). Each column is written by the one lane that
+ * owns it: the result does not depend on scheduling, and a second heal finds
+ * only the unresolved columns and stores nothing. Codes as for the scrub. */
+#define HRS_SCRUB_PATCHED 3
+
+/* Device-resident batch, arguments as hrs_scrub_dev; the rows are read and
+ * written. No row NULL and no two row pointers equal (HRS_EINVAL: a patch
+ * through one would change the other's column). Kernel mode 2 forces the
+ * byte-granular kernel. Asynchronous on stream. */
+hrs_status hrs_heal_dev(hrs_codec* codec, uint8_t* const* rows, size_t stride, size_t len, size_t nstripes,
+                        uint32_t* reports, size_t report_stride, void* stream);
+
+/* Same over a HOST batch laid out as for hrs_scrub_batch_host, cell-overlap
+ * rule included. Runtime-pinned stripes are healed in place by one launch (the
+ * few patched bytes cross the host link); any other memory is staged through
+ * the host-batch pipeline, and only the cells whose count in word 4 + l is
+ * nonzero are copied back: no other byte of the caller's memory is written.
+ * Synchronous. */
+hrs_status hrs_heal_batch_host(hrs_codec* codec, uint8_t* stripes, size_t row_stride, size_t stripe_stride,
+                               size_t len, size_t nstripes, uint32_t* reports, size_t report_stride);
+
+/* The same operation for one stripe of n HOST rows on the CPU (works on
+ * HRS_DEVICE_NONE handles): a plain loop over the columns through the locator
+ * the kernels run. report: 4 + n words. len == 0: nothing is touched. */
+hrs_status hrs_heal_host(const hrs_codec* codec, uint8_t* const* rows, size_t len, uint32_t* report);
 
 /* Kernel selection for tests and benchmarks: 0 = auto (default), 1 = force
  * the runtime-matrix bit-sliced kernel, 2 = force the byte-granular kernel,

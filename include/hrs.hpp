@@ -271,6 +271,30 @@ class HipReedSolomonCode : public HipCode {
                       uint32_t* reports, size_t reportStride) {
     check(hrs_scrub_batch_host(h_, stripes, rowStride, stripeStride, len, nstripes, reports, reportStride), h_);
   }
+
+  // Stripe healing (hrs_heal_dev): the scrub plus the write-back of every
+  // resolved column, in place; the reports describe the stripes as they were
+  // and word HRS_SCRUB_PATCHED counts the bytes stored. Asynchronous on stream.
+  void healDev(const std::vector<uint8_t*>& rows, size_t stride, size_t len, size_t nstripes, uint32_t* reports,
+               size_t reportStride, void* stream = nullptr) {
+    if (static_cast<int>(rows.size()) != stripeSize() + paritySize())
+      throw std::invalid_argument("healDev: row count does not match the codec");
+    check(hrs_heal_dev(h_, rows.data(), stride, len, nstripes, reports, reportStride, stream), h_);
+  }
+
+  // The same over a host batch (hrs_heal_batch_host); reports is a host array.
+  void healBatchHost(uint8_t* stripes, size_t rowStride, size_t stripeStride, size_t len, size_t nstripes,
+                     uint32_t* reports, size_t reportStride) {
+    check(hrs_heal_batch_host(h_, stripes, rowStride, stripeStride, len, nstripes, reports, reportStride), h_);
+  }
+
+  // One stripe of n host rows healed on the CPU (hrs_heal_host; host-only
+  // handles included); report holds HRS_SCRUB_HEAD + n words.
+  void healHost(const std::vector<uint8_t*>& rows, size_t len, uint32_t* report) {
+    if (static_cast<int>(rows.size()) != stripeSize() + paritySize())
+      throw std::invalid_argument("healHost: row count does not match the codec");
+    check(hrs_heal_host(h_, rows.data(), len, report), h_);
+  }
 };
 
 class HipXORCode : public HipCode {

@@ -44,6 +44,7 @@ EXPORTS = (
     "hrs_device_count", "hrs_codec_device", "hrs_decode_batch_host_multi", "hrs_encode_batch_host_multi",
     "hrs_set_timing", "hrs_ticket_gpu_ms", "hrs_last_host_path",
     "hrs_compute_error_locations", "hrs_scrub_dev", "hrs_scrub_batch_host",
+    "hrs_heal_dev", "hrs_heal_batch_host", "hrs_heal_host",
 )
 # include/hrs_probe.h, exported by libhrs_probe.so
 PROBE_EXPORTS = ("hrs_probe_stream", "hrs_probe_rows")
@@ -126,6 +127,9 @@ def lib():
         "hrs_compute_error_locations": ([P, IP, IP, IP, IP], I),
         "hrs_scrub_dev": ([P, PP, S, S, S, P, S, P], I),
         "hrs_scrub_batch_host": ([P, P, S, S, S, S, P, S], I),
+        "hrs_heal_dev": ([P, PP, S, S, S, P, S, P], I),
+        "hrs_heal_batch_host": ([P, P, S, S, S, S, P, S], I),
+        "hrs_heal_host": ([P, PP, S, P], I),
     }
     for name, (args, res) in sigs.items():
         f = getattr(L, name)

@@ -13,6 +13,7 @@
 #include <map>
 #include <string>
 #include <thread>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/hrs.h"
@@ -375,10 +376,21 @@ std::vector<RowRun> runs_of(const int* locs, int nlocs) {  // locs ascending
 // stripe s: rows at hin + s * in_stripe + l * in_row; outputs at
 // hout + s * out_stripe + t * out_row. out_rows_max may be 0 (the scrub
 // reads only): no output block, nothing copied back.
-template <typename Reads, typename Compute, typename Writes>
+// `dirty` (optional; the heal): for jobs whose kernels write into the image.
+// Once a chunk's kernels have finished, dirty(s0, ns, cells) lists the cells
+// (stripe index in the chunk, location) they changed; exactly those go back
+// from the slot's image to the caller's rows at hin, before the slot is
+// refilled: out of the pinned staging through the copy pool (zero copy), or
+// with a synchronous D2H out of the device image (copy engines; a rare path).
+struct DirtyCell {
+  size_t i;
+  int l;
+};
+template <typename Reads, typename Compute, typename Writes, typename Dirty = std::nullptr_t>
 hrs_status host_batch(hrs_codec* c, const uint8_t* hin, size_t in_row, size_t in_stripe, int img_rows, uint8_t* hout,
                       size_t out_row, size_t out_stripe, int out_rows_max, size_t len, size_t nstripes, Reads reads,
-                      Compute compute, Writes writes) {
+                      Compute compute, Writes writes, Dirty dirty = nullptr) {
+  constexpr bool has_dirty = !std::is_same_v<Dirty, std::nullptr_t>;
   const size_t dpitch = (len + 255) & ~static_cast<size_t>(255);
   const size_t img_stripe = dpitch * static_cast<size_t>(img_rows);
   const size_t out_stripe_dev = dpitch * static_cast<size_t>(out_rows_max);
@@ -415,6 +427,7 @@ hrs_status host_batch(hrs_codec* c, const uint8_t* hin, size_t in_row, size_t in
     bool used = false;  // the slot's events have been recorded by this call
     size_t s0 = 0, ns = 0;
   } pend[hrs::kHostBatchSlots];
+  std::vector<DirtyCell> cells;
   // wait for a slot; pageable: queue the copies of its outputs out of
   // staging in `jobs` (the caller runs them, merged with the slot's next
   // copy-in: the output block and the input image are disjoint)
@@ -431,6 +444,20 @@ hrs_status host_batch(hrs_codec* c, const uint8_t* hin, size_t in_row, size_t in
           jobs.push_back({hout + s * out_stripe + t * out_row, pout + i * out_stripe_dev + t * dpitch, len});
       }
     }
+    if constexpr (has_dirty) {
+      cells.clear();
+      hrs_status st = dirty(pend[sl].s0, pend[sl].ns, cells);
+      if (st != HRS_OK) return st;
+      for (const DirtyCell& d : cells) {
+        uint8_t* dst = const_cast<uint8_t*>(hin) + (pend[sl].s0 + d.i) * in_stripe + d.l * in_row;
+        const size_t at = d.i * img_stripe + d.l * dpitch;
+        if (zc) {
+          jobs.push_back({dst, h.pin + at, len});
+        } else if ((e = hipMemcpy(dst, h.dev + at, len, hipMemcpyDeviceToHost)) != hipSuccess) {
+          return hip_fail(c, e, "D2H of a healed cell");
+        }
+      }
+    }
     pend[sl].busy = false;
     return HRS_OK;
   };
@@ -439,14 +466,17 @@ hrs_status host_batch(hrs_codec* c, const uint8_t* hin, size_t in_row, size_t in
     const int sl = static_cast<int>(j % hrs::kHostBatchSlots);
     hrs_codec::HostBatchSlot& h = c->hbatch[sl];
     const size_t ns = std::min(chunk, nstripes - s0);
-    if (!pinned) {
+    if (!pinned || has_dirty) {
       jobs.clear();
       hrs_status st = finish(sl);
       if (st != HRS_OK) return st;
-      if (!merge && !jobs.empty()) {
+      // dirty cells leave the staging image before the next copy-in overwrites it
+      if ((!merge || has_dirty) && !jobs.empty()) {
         pool.run(jobs);
         jobs.clear();
       }
+    }
+    if (!pinned) {
       for (size_t i = 0; i < ns; ++i)
         for (const RowRun& r : reads(s0 + i))
           for (int q = 0; q < r.cnt; ++q) {
@@ -754,8 +784,12 @@ hrs_status encode_batch_host_impl(hrs_codec* c, uint8_t* stripes, size_t row_str
 // hrs_scrub_batch_host: every stripe's n rows are its reads, there are no
 // output rows; the reports accumulate in the handle's device buffer (dense,
 // 4 + n words per stripe) and come back in one copy.
+// heal (hrs_heal_batch_host): the heal kernels, which patch the image they
+// read. Pinned stripes are patched in place across the link; a staged chunk's
+// reports are fetched when its kernels have finished and the cells with a
+// nonzero count in word 4 + l go back to the caller (host_batch's dirty hook).
 hrs_status scrub_batch_host_impl(hrs_codec* c, const uint8_t* stripes, size_t row_stride, size_t stripe_stride,
-                                 size_t len, size_t nstripes, uint32_t* reports, size_t report_stride) {
+                                 size_t len, size_t nstripes, uint32_t* reports, size_t report_stride, bool heal) {
   DeviceGuard g(c->device);
   if (!g.ok) return fail(c, HRS_EDEVICE, "cannot select HIP device %d", c->device);
   const int n = c->n;
@@ -780,7 +814,7 @@ hrs_status scrub_batch_host_impl(hrs_codec* c, const uint8_t* stripes, size_t ro
     for (int l = 0; l < n; ++l) rows[l] = zs + static_cast<size_t>(l) * row_stride;
     {
       hrs::GridCap cap(zero_copy_blocks());
-      st = run_scrub(c, rows.data(), stripe_stride, len, nstripes, drep, nwords, hs);
+      st = run_scrub(c, rows.data(), stripe_stride, len, nstripes, drep, nwords, hs, heal);
     }
     if (st == HRS_OK) {
       const hipError_t e = hipStreamSynchronize(hs);
@@ -793,10 +827,23 @@ hrs_status scrub_batch_host_impl(hrs_codec* c, const uint8_t* stripes, size_t ro
     auto compute = [&](hipStream_t hs, size_t s0, size_t ns, uint8_t* dimg, size_t img_stripe, size_t dpitch, uint8_t*,
                        size_t) -> hrs_status {
       for (int l = 0; l < n; ++l) rows[l] = dimg + static_cast<size_t>(l) * dpitch;
-      return run_scrub(c, rows.data(), img_stripe, len, ns, drep + s0 * nwords, nwords, hs);
+      return run_scrub(c, rows.data(), img_stripe, len, ns, drep + s0 * nwords, nwords, hs, heal);
     };
-    st = host_batch(c, stripes, row_stride, stripe_stride, n, const_cast<uint8_t*>(stripes), row_stride,
-                    stripe_stride, 0, len, nstripes, reads, compute, writes);
+    std::vector<uint32_t> chunk_rep;
+    auto dirty = [&](size_t s0, size_t ns, std::vector<DirtyCell>& cells) -> hrs_status {
+      chunk_rep.resize(ns * nwords);
+      const hipError_t e = hipMemcpy(chunk_rep.data(), drep + s0 * nwords, ns * nwords * sizeof(uint32_t),
+                                     hipMemcpyDeviceToHost);
+      if (e != hipSuccess) return hip_fail(c, e, "hipMemcpy chunk reports");
+      for (size_t i = 0; i < ns; ++i)
+        for (int l = 0; l < n; ++l)
+          if (chunk_rep[i * nwords + hrs::kScrubHead + l] != 0) cells.push_back({i, l});
+      return HRS_OK;
+    };
+    st = heal ? host_batch(c, stripes, row_stride, stripe_stride, n, const_cast<uint8_t*>(stripes), row_stride,
+                           stripe_stride, 0, len, nstripes, reads, compute, writes, dirty)
+              : host_batch(c, stripes, row_stride, stripe_stride, n, const_cast<uint8_t*>(stripes), row_stride,
+                           stripe_stride, 0, len, nstripes, reads, compute, writes);
   }
   st = drain_hbatch(c, st);
   if (st != HRS_OK) return st;
@@ -808,12 +855,9 @@ hrs_status scrub_batch_host_impl(hrs_codec* c, const uint8_t* stripes, size_t ro
   return HRS_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-hrs_status hrs_scrub_batch_host(hrs_codec* c, const uint8_t* stripes, size_t row_stride, size_t stripe_stride,
-                                size_t len, size_t nstripes, uint32_t* reports, size_t report_stride) {
+// hrs_scrub_batch_host and hrs_heal_batch_host: one set of argument rules.
+hrs_status scrub_batch_host_entry(hrs_codec* c, const uint8_t* stripes, size_t row_stride, size_t stripe_stride,
+                                  size_t len, size_t nstripes, uint32_t* reports, size_t report_stride, bool heal) {
   if (!c) return HRS_EINVAL;
   hrs_status st = scrub_code_ok(c, report_stride, true);
   if (st != HRS_OK) return st;
@@ -831,13 +875,27 @@ hrs_status hrs_scrub_batch_host(hrs_codec* c, const uint8_t* stripes, size_t row
   if (row_stride < len || !stripes_apart)
     return fail(c, HRS_EINVAL, "cells overlap: row_stride %zu, stripe_stride %zu, len %zu, %d rows, %zu stripes",
                 row_stride, stripe_stride, len, c->n, nstripes);
-  st = scrub_batch_host_impl(c, stripes, row_stride, stripe_stride, len, nstripes, reports, report_stride);
+  st = scrub_batch_host_impl(c, stripes, row_stride, stripe_stride, len, nstripes, reports, report_stride, heal);
   if (st == HRS_OK) {
     DeviceGuard g(c->device);
     c->last_host_path =
         batch_path(g.ok && runtime_pinned(stripes, batch_span(nstripes, stripe_stride, c->n, row_stride, len)));
   }
   return st;
+}
+
+}  // namespace
+
+extern "C" {
+
+hrs_status hrs_scrub_batch_host(hrs_codec* c, const uint8_t* stripes, size_t row_stride, size_t stripe_stride,
+                                size_t len, size_t nstripes, uint32_t* reports, size_t report_stride) {
+  return scrub_batch_host_entry(c, stripes, row_stride, stripe_stride, len, nstripes, reports, report_stride, false);
+}
+
+hrs_status hrs_heal_batch_host(hrs_codec* c, uint8_t* stripes, size_t row_stride, size_t stripe_stride, size_t len,
+                               size_t nstripes, uint32_t* reports, size_t report_stride) {
+  return scrub_batch_host_entry(c, stripes, row_stride, stripe_stride, len, nstripes, reports, report_stride, true);
 }
 
 hrs_status hrs_decode_batch_dev(hrs_codec* c, const uint8_t* stripes, size_t row_stride, size_t stripe_stride,

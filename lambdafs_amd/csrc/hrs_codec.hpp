@@ -244,8 +244,12 @@ bool apply_crc_one_pass(const hrs_codec* c, int nout, int nlive, size_t len);
 hrs_status scrub_code_ok(hrs_codec* c, size_t report_stride, bool with_reports);
 // Empty reports, then the vector kernel over the whole 2 KiB windows and the
 // byte-granular kernel over the rest, all on stream s. rows[n]: none NULL.
+// heal: the kernels' heal variants, which also write the resolved columns
+// back through rows[] (writable, no two equal) and count the bytes in word 3.
 hrs_status run_scrub(hrs_codec* c, const uint8_t* const* rows, size_t stride, size_t len, size_t nstripes,
-                     uint32_t* reports, size_t report_stride, hipStream_t s);
+                     uint32_t* reports, size_t report_stride, hipStream_t s, bool heal);
+// The rows of a heal call: none NULL, no two equal (HRS_EINVAL).
+hrs_status heal_rows_ok(hrs_codec* c, const uint8_t* const* rows);
 
 }  // namespace hrs::api
 #pragma GCC visibility pop

@@ -98,6 +98,7 @@ hipError_t launch_batch_bitsliced(const BatchArgs& a, int max_nout, int max_nin,
 // ---- stripe scrubbing (hrs_scrub.hip): computeErrorLocations over every column
 
 constexpr int kScrubHead = 4;               // report words before the per-location counts (HRS_SCRUB_HEAD)
+constexpr int kScrubPatched = 3;            // heal only: bytes written back (HRS_SCRUB_PATCHED)
 constexpr uint32_t kScrubNone = 0xFFFFFFFFu;  // first-bad-column word of a clean stripe (HRS_SCRUB_NONE)
 constexpr int kScrubMaxRows = 255;          // hrs_create admits n = k + p <= 255 (ReedSolomonCode.java:57)
 
@@ -120,6 +121,11 @@ struct ScrubArgs {
 hipError_t launch_scrub_init(uint32_t* reports, uint64_t report_stride, int n, uint64_t nstripes, hipStream_t s);
 hipError_t launch_scrub(const ScrubArgs& a, hipStream_t s);
 hipError_t launch_scrub_bytewise(const ScrubArgs& a, hipStream_t s);
+// The same two launches with the write-back (hrs_heal_*): heal_kernel<P> and
+// heal_bytewise_kernel<P> store through rows[], which must be writable, and
+// add the bytes stored to report word 3.
+hipError_t launch_heal(const ScrubArgs& a, hipStream_t s);
+hipError_t launch_heal_bytewise(const ScrubArgs& a, hipStream_t s);
 
 // ---- stream gates of the queued host pipeline (hrs_gate.hip)
 // gate: waits until *ready (a coherent pinned word the host writes) reaches

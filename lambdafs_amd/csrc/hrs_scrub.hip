@@ -35,9 +35,14 @@ __device__ __forceinline__ void load_tables(uint8_t* s_exp, uint8_t* s_log) {
 
 // One bad column (syndromes s, not all zero) into the counters at h: a
 // per-wave LDS histogram (vector kernel) or the stripe's report itself.
-template <int P>
+// Heal: a resolved column is also written back, data[loc[j]] ^= err[j] at
+// rows[loc[j]] + at (ReedSolomonCode.java:281-285), one byte load, XOR and
+// byte store per nonzero error value, counted in word 3. An unresolved column
+// is not touched (the Java returns false after writing it; include/hrs.h).
+// The column belongs to this lane alone, so the stores race with nothing.
+template <int P, bool Heal>
 __device__ __forceinline__ void count_column(const locator::Field& f, int n, const uint8_t (&s)[P], uint32_t col,
-                                             uint32_t* h) {
+                                             uint32_t* h, const uint8_t* const* rows, uint64_t at) {
   int nloc = 0;
   uint8_t loc[locator::kMaxErrors], err[locator::kMaxErrors];
   const bool resolved = locator::locate(f, n, P, s, &nloc, loc, err);
@@ -47,12 +52,26 @@ __device__ __forceinline__ void count_column(const locator::Field& f, int n, con
     atomicAdd(&h[1], 1u);
   } else {
     for (int j = 0; j < nloc; ++j) atomicAdd(&h[kScrubHead + loc[j]], 1u);
+    if constexpr (Heal) {
+      uint32_t patched = 0u;
+      for (int j = 0; j < nloc; ++j)
+        if (err[j] != 0) {
+          uint8_t* q = const_cast<uint8_t*>(rows[loc[j]]) + at;
+          *q = static_cast<uint8_t>(*q ^ err[j]);
+          ++patched;
+        }
+      if (patched != 0u) atomicAdd(&h[kScrubPatched], patched);
+    }
   }
 }
 
 // ------------------------------------------------------ vector kernel
 
-template <int P>
+// Heal = false is the scrub as it always was (hrs_last_kernel "scrub_kernel<P>").
+// Heal = true adds the write-back of the resolved columns (hrs_heal_dev,
+// "heal_kernel<P>"): the clean-window path is the same code, the stores sit
+// behind the ballot in count_column.
+template <int P, bool Heal = false>
 __global__ void __launch_bounds__(kBlockThreads) scrub_kernel(const ScrubArgs a) {
   __shared__ uint8_t s_exp[512];
   __shared__ uint8_t s_log[256];
@@ -134,7 +153,7 @@ __global__ void __launch_bounds__(kBlockThreads) scrub_kernel(const ScrubArgs a)
           }
           if (nz == 0u) continue;
           const uint32_t col = static_cast<uint32_t>(off) + (x >> 2) * 1024u + lane * 16u + (x & 3) * 4u + b;
-          count_column<P>(f, a.n, s, col, hist);
+          count_column<P, Heal>(f, a.n, s, col, hist, a.rows, stripe * a.stride + col);
         }
       }
     }
@@ -159,7 +178,7 @@ __global__ void __launch_bounds__(kBlockThreads) scrub_kernel(const ScrubArgs a)
 // One column per lane, tables in LDS: rows or strides that are not 16-byte
 // aligned, the row tail (len % 2 KiB) and kernel mode 2. Task idx = stripe *
 // (len - col0) + (column - col0). Counts go straight into the report.
-template <int P>
+template <int P, bool Heal = false>
 __global__ void __launch_bounds__(kBlockThreads) scrub_bytewise_kernel(const ScrubArgs a) {
   __shared__ uint8_t s_exp[512];
   __shared__ uint8_t s_log[256];
@@ -181,7 +200,7 @@ __global__ void __launch_bounds__(kBlockThreads) scrub_bytewise_kernel(const Scr
 #pragma unroll
     for (int i = 0; i < P; ++i) nz |= s[i];
     if (nz == 0u) continue;
-    count_column<P>(f, a.n, s, static_cast<uint32_t>(col), a.reports + stripe * a.report_stride);
+    count_column<P, Heal>(f, a.n, s, static_cast<uint32_t>(col), a.reports + stripe * a.report_stride, a.rows, at);
   }
 }
 
@@ -196,18 +215,18 @@ __global__ void __launch_bounds__(kBlockThreads) scrub_init_kernel(uint32_t* rep
   }
 }
 
-template <int P>
-hipError_t launch_scrub_p(const ScrubArgs& a, hipStream_t s) {
-  auto kern = scrub_kernel<P>;
-  note_kernel_t("scrub_kernel", P);
+template <int P, bool Heal>
+hipError_t launch_windows(const ScrubArgs& a, hipStream_t s) {
+  auto kern = scrub_kernel<P, Heal>;
+  note_kernel_t(Heal ? "heal_kernel" : "scrub_kernel", P);
   hipLaunchKernelGGL(kern, dim3(stream_grid(a.ntasks)), dim3(kBlockThreads), 0, s, with_order(a, kOrderScrub));
   return hipGetLastError();
 }
 
-template <int P>
-hipError_t launch_scrub_bytewise_p(const ScrubArgs& a, hipStream_t s) {
-  auto kern = scrub_bytewise_kernel<P>;
-  note_kernel_t("scrub_bytewise_kernel", P);
+template <int P, bool Heal>
+hipError_t launch_columns(const ScrubArgs& a, hipStream_t s) {
+  auto kern = scrub_bytewise_kernel<P, Heal>;
+  note_kernel_t(Heal ? "heal_bytewise_kernel" : "scrub_bytewise_kernel", P);
   const unsigned g = grid_for(kern, kBlockThreads, a.ntasks);
   hipLaunchKernelGGL(kern, dim3(g), dim3(kBlockThreads), 0, s, a);
   return hipGetLastError();
@@ -223,22 +242,26 @@ hipError_t launch_scrub_init(uint32_t* reports, uint64_t report_stride, int n, u
   return hipGetLastError();
 }
 
-#define HRS_SCRUB_DISPATCH(fn)        \
-  switch (a.p) {                      \
-    case 1: return fn<1>(a, s);       \
-    case 2: return fn<2>(a, s);       \
-    case 3: return fn<3>(a, s);       \
-    case 4: return fn<4>(a, s);       \
-    case 5: return fn<5>(a, s);       \
-    case 6: return fn<6>(a, s);       \
-    case 7: return fn<7>(a, s);       \
-    case 8: return fn<8>(a, s);       \
-    default: return hipErrorInvalidValue; \
+#define HRS_SCRUB_DISPATCH(fn, heal)         \
+  switch (a.p) {                             \
+    case 1: return fn<1, heal>(a, s);        \
+    case 2: return fn<2, heal>(a, s);        \
+    case 3: return fn<3, heal>(a, s);        \
+    case 4: return fn<4, heal>(a, s);        \
+    case 5: return fn<5, heal>(a, s);        \
+    case 6: return fn<6, heal>(a, s);        \
+    case 7: return fn<7, heal>(a, s);        \
+    case 8: return fn<8, heal>(a, s);        \
+    default: return hipErrorInvalidValue;    \
   }
 
-hipError_t launch_scrub(const ScrubArgs& a, hipStream_t s) { HRS_SCRUB_DISPATCH(launch_scrub_p) }
+hipError_t launch_scrub(const ScrubArgs& a, hipStream_t s) { HRS_SCRUB_DISPATCH(launch_windows, false) }
 
-hipError_t launch_scrub_bytewise(const ScrubArgs& a, hipStream_t s) { HRS_SCRUB_DISPATCH(launch_scrub_bytewise_p) }
+hipError_t launch_scrub_bytewise(const ScrubArgs& a, hipStream_t s) { HRS_SCRUB_DISPATCH(launch_columns, false) }
+
+hipError_t launch_heal(const ScrubArgs& a, hipStream_t s) { HRS_SCRUB_DISPATCH(launch_windows, true) }
+
+hipError_t launch_heal_bytewise(const ScrubArgs& a, hipStream_t s) { HRS_SCRUB_DISPATCH(launch_columns, true) }
 
 #undef HRS_SCRUB_DISPATCH
 

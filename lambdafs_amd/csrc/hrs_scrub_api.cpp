@@ -1,7 +1,8 @@
-// Stripe scrubbing behind the C ABI: the scalar computeErrorLocations on the
-// host (hrs_compute_error_locations, host-only handles included) and the
-// device-resident batch (hrs_scrub_dev). The host-memory batch is in
-// hrs_batch_api.cpp beside the pipeline it shares. The per-column algorithm
+// Stripe scrubbing and healing behind the C ABI: the scalar
+// computeErrorLocations on the host (hrs_compute_error_locations, host-only
+// handles included), the device-resident batches (hrs_scrub_dev, hrs_heal_dev)
+// and one stripe healed on the CPU (hrs_heal_host). The host-memory batches are
+// in hrs_batch_api.cpp beside the pipeline they share. The per-column algorithm
 // is hrs_locator.hpp, the same code the kernels of hrs_scrub.hip run.
 #include <hip/hip_runtime.h>
 
@@ -39,7 +40,7 @@ hrs_status scrub_code_ok(hrs_codec* c, size_t report_stride, bool with_reports) 
 }
 
 hrs_status run_scrub(hrs_codec* c, const uint8_t* const* rows, size_t stride, size_t len, size_t nstripes,
-                     uint32_t* reports, size_t report_stride, hipStream_t s) {
+                     uint32_t* reports, size_t report_stride, hipStream_t s, bool heal) {
   hipError_t e = hrs::launch_scrub_init(reports, report_stride, c->n, nstripes, s);
   if (e != hipSuccess) return hip_fail(c, e, "scrub init launch");
   hrs::ScrubArgs a{};
@@ -57,17 +58,58 @@ hrs_status run_scrub(hrs_codec* c, const uint8_t* const* rows, size_t stride, si
   a.nwin = vec_ok ? len / hrs::kWindowBytes : 0;
   if (a.nwin > 0) {
     a.ntasks = a.nwin * nstripes;
-    e = hrs::launch_scrub(a, s);
-    if (e != hipSuccess) return hip_fail(c, e, "scrub launch");
+    e = heal ? hrs::launch_heal(a, s) : hrs::launch_scrub(a, s);
+    if (e != hipSuccess) return hip_fail(c, e, heal ? "heal launch" : "scrub launch");
     c->last_kernel = hrs::last_kernel();
   }
   a.col0 = a.nwin * hrs::kWindowBytes;
   if (a.col0 < len) {
     a.ntasks = (len - a.col0) * nstripes;
-    e = hrs::launch_scrub_bytewise(a, s);
-    if (e != hipSuccess) return hip_fail(c, e, "scrub bytewise launch");
+    e = heal ? hrs::launch_heal_bytewise(a, s) : hrs::launch_scrub_bytewise(a, s);
+    if (e != hipSuccess) return hip_fail(c, e, heal ? "heal bytewise launch" : "scrub bytewise launch");
     if (a.nwin == 0) c->last_kernel = hrs::last_kernel();
   }
+  return HRS_OK;
+}
+
+namespace {
+
+// One stripe on the CPU: the column loop of hrs_heal_host.
+template <int P>
+void heal_stripe(const hrs::locator::Field& f, int n, uint8_t* const* rows, size_t len, uint32_t* rep) {
+  for (size_t col = 0; col < len; ++col) {
+    uint8_t s[P] = {};
+    for (int l = n - 1; l >= 0; --l) hrs::locator::horner_step<P>(f, s, rows[l][col]);
+    uint32_t nz = 0;
+    for (int i = 0; i < P; ++i) nz |= s[i];
+    if (nz == 0) continue;
+    int nloc = 0;
+    uint8_t loc[hrs::locator::kMaxErrors], err[hrs::locator::kMaxErrors];
+    const bool resolved = hrs::locator::locate(f, n, P, s, &nloc, loc, err);
+    ++rep[HRS_SCRUB_BAD];
+    if (rep[HRS_SCRUB_FIRST_BAD] == HRS_SCRUB_NONE) rep[HRS_SCRUB_FIRST_BAD] = static_cast<uint32_t>(col);
+    if (!resolved) {  // left as it is, even where the Java wrote into it before returning false
+      ++rep[HRS_SCRUB_UNRESOLVED];
+      continue;
+    }
+    for (int j = 0; j < nloc; ++j) {
+      ++rep[HRS_SCRUB_HEAD + loc[j]];
+      if (err[j] == 0) continue;  // a blamed location whose value stands: nothing to store
+      rows[loc[j]][col] ^= err[j];
+      ++rep[HRS_SCRUB_PATCHED];
+    }
+  }
+}
+
+}  // namespace
+
+// A patch through one of two equal row pointers would change the other's column.
+hrs_status heal_rows_ok(hrs_codec* c, const uint8_t* const* rows) {
+  for (int l = 0; l < c->n; ++l)
+    if (!rows[l]) return fail(c, HRS_EINVAL, "row %d is NULL", l);
+  for (int l = 1; l < c->n; ++l)
+    for (int m = 0; m < l; ++m)
+      if (rows[l] == rows[m]) return fail(c, HRS_EINVAL, "rows %d and %d are one pointer: healing writes the rows", m, l);
   return HRS_OK;
 }
 
@@ -130,7 +172,48 @@ hrs_status hrs_scrub_dev(hrs_codec* c, const uint8_t* const* rows, size_t stride
   if (len == 0 || nstripes == 0) return HRS_OK;
   DeviceGuard g(c->device);
   if (!g.ok) return fail(c, HRS_EDEVICE, "cannot select HIP device %d", c->device);
-  return run_scrub(c, rows, stride, len, nstripes, reports, report_stride, static_cast<hipStream_t>(stream));
+  return run_scrub(c, rows, stride, len, nstripes, reports, report_stride, static_cast<hipStream_t>(stream), false);
+}
+
+hrs_status hrs_heal_dev(hrs_codec* c, uint8_t* const* rows, size_t stride, size_t len, size_t nstripes,
+                        uint32_t* reports, size_t report_stride, void* stream) {
+  if (!c) return HRS_EINVAL;
+  hrs_status st = scrub_code_ok(c, report_stride, true);
+  if (st != HRS_OK) return st;
+  if (!rows || !reports) return fail(c, HRS_EINVAL, "rows or reports is NULL");
+  st = heal_rows_ok(c, rows);
+  if (st != HRS_OK) return st;
+  if (nstripes > 0x7fffffffu) return fail(c, HRS_EINVAL, "too many stripes");
+  if (len > 0xffffffffu) return fail(c, HRS_EINVAL, "rows of %zu bytes: column indices are 32-bit", len);
+  if (len == 0 || nstripes == 0) return HRS_OK;
+  DeviceGuard g(c->device);
+  if (!g.ok) return fail(c, HRS_EDEVICE, "cannot select HIP device %d", c->device);
+  return run_scrub(c, rows, stride, len, nstripes, reports, report_stride, static_cast<hipStream_t>(stream), true);
+}
+
+hrs_status hrs_heal_host(const hrs_codec* cc, uint8_t* const* rows, size_t len, uint32_t* report) {
+  auto* c = const_cast<hrs_codec*>(cc);
+  if (!c) return HRS_EINVAL;
+  hrs_status st = scrub_code_ok(c, 0, false);
+  if (st != HRS_OK) return st;
+  if (!rows || !report) return fail(c, HRS_EINVAL, "rows or report is NULL");
+  st = heal_rows_ok(c, rows);
+  if (st != HRS_OK) return st;
+  if (len > 0xffffffffu) return fail(c, HRS_EINVAL, "rows of %zu bytes: column indices are 32-bit", len);
+  if (len == 0) return HRS_OK;
+  for (int e = 0; e < HRS_SCRUB_HEAD + c->n; ++e) report[e] = e == HRS_SCRUB_FIRST_BAD ? HRS_SCRUB_NONE : 0u;
+  const hrs::locator::Field f{kHostTables.exp, kHostTables.log};
+  switch (c->p) {
+    case 1: heal_stripe<1>(f, c->n, rows, len, report); break;
+    case 2: heal_stripe<2>(f, c->n, rows, len, report); break;
+    case 3: heal_stripe<3>(f, c->n, rows, len, report); break;
+    case 4: heal_stripe<4>(f, c->n, rows, len, report); break;
+    case 5: heal_stripe<5>(f, c->n, rows, len, report); break;
+    case 6: heal_stripe<6>(f, c->n, rows, len, report); break;
+    case 7: heal_stripe<7>(f, c->n, rows, len, report); break;
+    default: heal_stripe<8>(f, c->n, rows, len, report); break;
+  }
+  return HRS_OK;
 }
 
 }  // extern "C"

@@ -281,15 +281,16 @@ def crc32_rows(code, row_views, crc_in=None):
 
 
 SCRUB_BAD, SCRUB_UNRESOLVED, SCRUB_FIRST_BAD, SCRUB_HEAD = 0, 1, 2, 4  # report words (include/hrs.h)
+SCRUB_PATCHED = 3  # heal only: bytes written back
 SCRUB_NONE = 0xFFFFFFFF
 
 
-def _scrub(code, rows, stride, L, S, ref):
+def _scrub(code, rows, stride, L, S, ref, heal=False):
     torch = _lib.torch
     n = code.stripeSize() + code.paritySize()
     reports = torch.empty((S, SCRUB_HEAD + n), dtype=torch.int32, device=ref.device)
-    code._check(_lib.lib().hrs_scrub_dev(code._handle(), rows, stride, L, S, reports.data_ptr(), SCRUB_HEAD + n,
-                                         _stream(ref)))
+    call = _lib.lib().hrs_heal_dev if heal else _lib.lib().hrs_scrub_dev
+    code._check(call(code._handle(), rows, stride, L, S, reports.data_ptr(), SCRUB_HEAD + n, _stream(ref)))
     return reports
 
 
@@ -327,6 +328,44 @@ def scrub_batch_host(code, stripes):
     reports = np.zeros((S, SCRUB_HEAD + n), dtype=np.uint32)
     code._check(_lib.lib().hrs_scrub_batch_host(code._handle(), sp, sstr[1], sstr[0], L, S, reports.ctypes.data,
                                                 SCRUB_HEAD + n))
+    return reports
+
+
+def heal_stripes(code, stripes):
+    """scrub_stripes plus the write-back (hrs_heal_dev): every column that
+    computeErrorLocations resolves is rewritten in place to the method's
+    post-call data, unresolved columns are left as they are. Returns the
+    reports of the stripes as they were; word SCRUB_PATCHED counts the bytes
+    stored."""
+    n = code.stripeSize() + code.paritySize()
+    if stripes.dim() != 3 or stripes.shape[1] != n:
+        raise ValueError(f"stripes must be [S, {n}, L]")
+    rows, stride, L, S = _stripe_rows(stripes, range(n))
+    return _scrub(code, rows, stride, L, S, stripes, heal=True)
+
+
+def heal_rows(code, row_views):
+    """heal_stripes with explicit [S, L] row views, one per location in hops order."""
+    n = code.stripeSize() + code.paritySize()
+    if len(row_views) != n or any(v is None for v in row_views):
+        raise ValueError(f"need {n} row views")
+    rows, stride, L, S = _rows(row_views)
+    return _scrub(code, rows, stride, L, S, row_views[0], heal=True)
+
+
+def heal_batch_host(code, stripes):
+    """hrs_heal_batch_host: heal_stripes for stripes[S, n, L] in HOST memory
+    (numpy array or CPU tensor, healed in place; of staged memory only the
+    cells that held a resolved error are written): a numpy uint32 array
+    [S, 4 + n]."""
+    n = code.stripeSize() + code.paritySize()
+    sp, sshape, sstr = _host_ptr(stripes, "stripes", writable=True)
+    if len(sshape) != 3 or sshape[1] != n or sstr[2] != 1:
+        raise ValueError(f"stripes must be [S, {n}, L] with unit byte stride")
+    S, L = sshape[0], sshape[2]
+    reports = np.zeros((S, SCRUB_HEAD + n), dtype=np.uint32)
+    code._check(_lib.lib().hrs_heal_batch_host(code._handle(), sp, sstr[1], sstr[0], L, S, reports.ctypes.data,
+                                               SCRUB_HEAD + n))
     return reports
 
 
