@@ -105,8 +105,15 @@ void hrs_destroy(hrs_codec* codec);
 const char* hrs_last_error(const hrs_codec* codec);
 /* Name of the main kernel the handle's latest coding call launched, as
  * rocprofv3 prints it without its namespace and parameters (e.g.
- * "encode_static_kernel<10, 4>"); "" before any device work. Lets a
- * benchmark attach the PMC traffic of the kernel it actually ran. */
+ * "encode_static_kernel<10, 4>"); "" before any device work. A call that
+ * launches a vector kernel and a byte-granular kernel for the row tails names
+ * the vector kernel (with several vector launches, the last one); a call whose
+ * only launch is the byte-granular kernel (rows or strides off 16-byte
+ * boundaries, rows shorter than 2 KiB, kernel mode 2) names that one
+ * ("bytewise_kernel", "batch_bytewise_kernel"); a call that launches no kernel
+ * (hrs_apply_dev with an all-zero matrix) sets "". hrs_crc32_dev leaves the
+ * name alone. Lets a benchmark attach the PMC traffic of the kernel it
+ * actually ran. */
 const char* hrs_last_kernel(const hrs_codec* codec);
 /* How the handle's latest synchronous host-buffer call (hrs_encode, hrs_decode,
  * hrs_decode3, hrs_*_crc) or host batch (hrs_*_batch_host) moved its bytes:

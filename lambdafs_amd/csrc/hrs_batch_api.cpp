@@ -142,6 +142,7 @@ hrs_status launch_batch(hrs_codec* c, const BatchPlanSet& ps, const hrs::BatchPl
     a.ntasks = (len - a.col0) * ns;
     hipError_t e = hrs::launch_batch_bytewise(a, hs);
     if (e != hipSuccess) return hip_fail(c, e, "batch bytewise launch");
+    if (a.nwin == 0) c->last_kernel = hrs::last_kernel();  // the call's only kernel
   }
   return HRS_OK;
 }

@@ -62,6 +62,7 @@ hrs_status run_apply(hrs_codec* c, const uint8_t* m, int nout, int nin, const ui
         hipError_t e = hipMemsetAsync(out_rows[o] + st * out_stride, 0, len, s);
         if (e != hipSuccess) return hip_fail(c, e, "hipMemsetAsync");
       }
+    c->last_kernel.clear();  // no kernel ran
     return HRS_OK;
   }
 
@@ -87,8 +88,13 @@ hrs_status run_apply(hrs_codec* c, const uint8_t* m, int nout, int nin, const ui
       std::vector<uint8_t*> tout(nout);
       for (int i = 0; i < nin; ++i) tin[i] = in_rows[i] + tail_off;
       for (int o = 0; o < nout; ++o) tout[o] = out_rows[o] + tail_off;
-      // tail < one window: run_apply sends it to the byte-granular kernel
-      return run_apply(c, m, nout, nin, tin.data(), in_stride, tout.data(), out_stride, tail, nstripes, s, false);
+      // tail < one window: run_apply sends it to the byte-granular kernel;
+      // the call keeps naming the static kernel
+      const std::string main_kernel = c->last_kernel;
+      const hrs_status st =
+          run_apply(c, m, nout, nin, tin.data(), in_stride, tout.data(), out_stride, tail, nstripes, s, false);
+      c->last_kernel = main_kernel;
+      return st;
     }
   }
 
@@ -178,6 +184,7 @@ hrs_status run_apply(hrs_codec* c, const uint8_t* m, int nout, int nin, const ui
         b.ntasks = tail * nstripes;
         hipError_t e = hrs::launch_bytewise(b, s);
         if (e != hipSuccess) return hip_fail(c, e, "bytewise launch");
+        if (nwin == 0) c->last_kernel = hrs::last_kernel();  // the call's only kernel
       }
     }
   }

@@ -253,7 +253,12 @@ class _HipErasureCode(ErasureCode):
     # -- matrices (host)
     def lastKernel(self):
         """Main kernel of this handle's latest coding call, as rocprofv3 names
-        it (hrs_last_kernel); "" before any device work."""
+        it (hrs_last_kernel); "" before any device work. The vector kernel
+        when the call also ran the byte-granular kernel for the row tails; the
+        byte-granular kernel ("bytewise_kernel", "batch_bytewise_kernel") when
+        that was the call's only launch (unaligned rows, rows under 2 KiB,
+        kernel mode 2); "" after a call that launched no kernel (an all-zero
+        matrix). crc32_rows does not change it."""
         return _lib.lib().hrs_last_kernel(self._handle()).decode()
 
     def lastHostPath(self):

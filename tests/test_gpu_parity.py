@@ -110,6 +110,7 @@ def test_unaligned_rows_use_bytewise_kernel(cuda):
     par = [torch.zeros(L + 3, dtype=torch.uint8, device="cuda")[3:] for _ in range(p)]
     code.encodeBulk(data, par)
     torch.cuda.synchronize()
+    assert code.lastKernel() == "bytewise_kernel"
     ref = C.encode_bulk(k, p, [d.cpu().numpy() for d in data])
     assert all((a.cpu().numpy() == b).all() for a, b in zip(par, ref))
 
