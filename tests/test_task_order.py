@@ -2,9 +2,12 @@
 grid-stride, 0 = block range, C > 1 = block-cyclic chunks of C windows per
 wave) against the oracle on task counts that do not divide evenly: fewer
 tasks than one block's waves, a last block with a short range, ranges that are not a multiple of the block's waves, and
-row tails (the byte-granular kernel) beside whole windows. Every streaming
-kernel family: static encode, fused encode + CRC, the pipelined and plain
-repairs, fused repair + CRC, the heterogeneous repair batch, CRC-32 windows.
+row tails (the byte-granular kernel) beside whole windows. The streaming
+kernel families that write coded bytes or CRCs: static encode, fused encode +
+CRC, the pipelined and plain repairs, fused repair + CRC, the heterogeneous
+repair batch, CRC-32 windows. The scrub and heal kernels take the same orders
+(kOrderScrub); tests/test_gpu_scrub_waves.py runs them under each, against
+the oracle, with several dirty windows per wave.
 Bar: bit-exact. EVERY stripe is checked (a window an order misses or
 runs twice in the middle of the task range must not slip through): coded
 bytes against the byte-granular kernel (kernel mode 2, one byte column per
