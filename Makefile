@@ -70,6 +70,10 @@ build/hrs_decode_crc.o: lambdafs_amd/csrc/hrs_decode_crc.hip $(HDRS)
 	@mkdir -p build
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
+build/hrs_batch_crc.o: lambdafs_amd/csrc/hrs_batch_crc.hip $(HDRS)
+	@mkdir -p build
+	$(HIPCC) $(HIPFLAGS) -c $< -o $@
+
 build/hrs_gate.o: lambdafs_amd/csrc/hrs_gate.hip $(HDRS)
 	@mkdir -p build
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
@@ -83,7 +87,7 @@ build/hrs_probe.o: lambdafs_amd/csrc/hrs_probe.hip include/hrs_probe.h $(HDRS)
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
 KOBJ     := build/hrs_kernels.o build/hrs_runtime.o build/hrs_batch.o build/hrs_crc.o build/hrs_fused.o build/hrs_decode_crc.o \
-            build/hrs_gate.o build/hrs_scrub.o
+            build/hrs_batch_crc.o build/hrs_gate.o build/hrs_scrub.o
 
 $(LIB): $(API_OBJ) $(KOBJ) lambdafs_amd/csrc/libhrs.map
 	$(HIPCC) $(HIPFLAGS) -shared -Wl,--version-script=lambdafs_amd/csrc/libhrs.map -o $@ $(API_OBJ) $(KOBJ) \

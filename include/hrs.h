@@ -416,6 +416,56 @@ hrs_status hrs_decode_crc_dev(hrs_codec* codec, const uint8_t* const* rows, size
                               const int* not_to_read, int num_not_to_read, size_t len, size_t nstripes,
                               const uint32_t* crc_in, uint32_t* crc_out, void* stream);
 
+/* ---- batches + CRC-32: the block checksums of the many-stripe calls ----
+ * Encoder.encodeStripe checksums every source and parity cell
+ * (Encoder.java:408-450) and the Decoder compares every repaired block's CRC32
+ * with the NameNode's (Decoder.java:222-229, :645-655); these are the batch
+ * calls above with those CRCs computed in the same pass. Common rules:
+ *  - the bytes written to `out` / the stripes are exactly those of the call
+ *    without CRCs: same layout, survivor choice, HRS_ETOOMANY, bytes left
+ *    untouched, for every code family;
+ *  - crc_out[i] is the zlib CRC-32 of cell i continued from crc_in[i]
+ *    (CRC32.update chaining; crc_in NULL = a fresh CRC32);
+ *  - crc_out may be the same array as crc_in; any other overlap of the two is
+ *    HRS_EINVAL; a NULL crc_out with work to do is HRS_EINVAL;
+ *  - len == 0 or nstripes == 0 (decode: or max_erased == 0) returns HRS_OK
+ *    and touches nothing, the CRC arrays included;
+ *  - argument errors are reported before the device is selected; a host-only
+ *    handle with valid arguments gets HRS_EDEVICE;
+ *  - hrs_last_kernel and hrs_last_host_path behave as for the sibling call. */
+
+/* hrs_decode_batch_dev + the CRC-32 of every repaired cell.
+ * crc_in / crc_out: DEVICE uint32 [nstripes * max_erased];
+ * crc_out[s * max_erased + t] belongs to output t of stripe s. For t >= the
+ * stripe's number of losses (a stripe that lost nothing included) the CRC is
+ * continued over no bytes: crc_out = crc_in, or 0 when crc_in is NULL.
+ * Batches of <= 4 losses per stripe from <= 12 live survivors (<= 8 at 4
+ * losses), len a multiple of 2 KiB, base pointers and the four strides
+ * 16-byte aligned take one fused kernel (each repaired cell written once,
+ * never read back); anything else runs hrs_decode_batch_dev, then the CRC pass
+ * over `out` (which reads, and discards, the rows past a stripe's losses),
+ * with identical results. Asynchronous on `stream`. */
+hrs_status hrs_decode_batch_crc_dev(hrs_codec* codec, const uint8_t* stripes, size_t row_stride,
+                                    size_t stripe_stride, const int* erased, int max_erased, uint8_t* out,
+                                    size_t out_row_stride, size_t out_stripe_stride, size_t len,
+                                    size_t nstripes, const uint32_t* crc_in, uint32_t* crc_out, void* stream);
+
+/* hrs_decode_batch_host + the same CRCs, computed on the GPU as the chunks
+ * pass through it; crc_in / crc_out are HOST uint32 [nstripes * max_erased]
+ * (read before the first chunk, written once after the last). Synchronous. */
+hrs_status hrs_decode_batch_host_crc(hrs_codec* codec, const uint8_t* stripes, size_t row_stride,
+                                     size_t stripe_stride, const int* erased, int max_erased, uint8_t* out,
+                                     size_t out_row_stride, size_t out_stripe_stride, size_t len,
+                                     size_t nstripes, const uint32_t* crc_in, uint32_t* crc_out);
+
+/* hrs_encode_batch_host + the CRC-32 of all k + p cells of every stripe;
+ * crc_in / crc_out are HOST uint32 [nstripes * (k + p)], ordered as
+ * hrs_encode_crc_dev: crc_out[s * (k + p) + r] is data row r (hops location
+ * p + r) for r < k and parity row r - k for r >= k. The shapes
+ * hrs_encode_crc_dev fuses take its one-pass kernel per chunk. Synchronous. */
+hrs_status hrs_encode_batch_host_crc(hrs_codec* codec, uint8_t* stripes, size_t row_stride, size_t stripe_stride,
+                                     size_t len, size_t nstripes, const uint32_t* crc_in, uint32_t* crc_out);
+
 /* ---- stripe scrubbing: ReedSolomonCode.computeErrorLocations in bulk ----
  * Whether a stripe at rest is still a codeword, and which cells went bad when
  * nothing reported an erasure. For each byte column c of each stripe the

@@ -204,6 +204,30 @@ class HipCode : public ErasureCode {
     check(hrs_collect(h_, ticket, outputs.data(), crcs ? crcs->data() : nullptr), h_);
   }
 
+  // The batch calls with block checksums (hrs_decode_batch_crc_dev,
+  // hrs_decode_batch_host_crc, hrs_encode_batch_host_crc; layout and semantics
+  // in include/hrs.h). crcIn may be nullptr (fresh CRC32s) or crcOut itself.
+  void decodeBatchCrcDev(const uint8_t* stripes, size_t rowStride, size_t stripeStride, const int* erased,
+                         int maxErased, uint8_t* out, size_t outRowStride, size_t outStripeStride, size_t len,
+                         size_t nstripes, const uint32_t* crcIn, uint32_t* crcOut, void* stream) {
+    check(hrs_decode_batch_crc_dev(h_, stripes, rowStride, stripeStride, erased, maxErased, out, outRowStride,
+                                   outStripeStride, len, nstripes, crcIn, crcOut, stream),
+          h_);
+  }
+
+  void decodeBatchHostCrc(const uint8_t* stripes, size_t rowStride, size_t stripeStride, const int* erased,
+                          int maxErased, uint8_t* out, size_t outRowStride, size_t outStripeStride, size_t len,
+                          size_t nstripes, const uint32_t* crcIn, uint32_t* crcOut) {
+    check(hrs_decode_batch_host_crc(h_, stripes, rowStride, stripeStride, erased, maxErased, out, outRowStride,
+                                    outStripeStride, len, nstripes, crcIn, crcOut),
+          h_);
+  }
+
+  void encodeBatchHostCrc(uint8_t* stripes, size_t rowStride, size_t stripeStride, size_t len, size_t nstripes,
+                          const uint32_t* crcIn, uint32_t* crcOut) {
+    check(hrs_encode_batch_host_crc(h_, stripes, rowStride, stripeStride, len, nstripes, crcIn, crcOut), h_);
+  }
+
   // RS-specific decodeBulk(readBufs, writeBufs, erasedLocation), ReedSolomonCode.java:168-185.
   void decodeBulk3(const std::vector<uint8_t*>& readBufs, const std::vector<uint8_t*>& writeBufs, size_t len,
                    const std::vector<int>& erased) {

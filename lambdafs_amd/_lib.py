@@ -45,6 +45,7 @@ EXPORTS = (
     "hrs_set_timing", "hrs_ticket_gpu_ms", "hrs_last_host_path",
     "hrs_compute_error_locations", "hrs_scrub_dev", "hrs_scrub_batch_host",
     "hrs_heal_dev", "hrs_heal_batch_host", "hrs_heal_host",
+    "hrs_decode_batch_crc_dev", "hrs_decode_batch_host_crc", "hrs_encode_batch_host_crc",
 )
 # include/hrs_probe.h, exported by libhrs_probe.so
 PROBE_EXPORTS = ("hrs_probe_stream", "hrs_probe_rows")
@@ -108,6 +109,9 @@ def lib():
         "hrs_decode_crc_dev": ([P, PP, S, PP, S, IP, I, IP, I, S, S, P, P, P], I),
         "hrs_decode_batch_host": ([P, P, S, S, P, I, P, S, S, S, S], I),
         "hrs_encode_batch_host": ([P, P, S, S, S, S], I),
+        "hrs_decode_batch_crc_dev": ([P, P, S, S, P, I, P, S, S, S, S, P, P, P], I),
+        "hrs_decode_batch_host_crc": ([P, P, S, S, P, I, P, S, S, S, S, P, P], I),
+        "hrs_encode_batch_host_crc": ([P, P, S, S, S, S, P, P], I),
         "hrs_decode_batch_host_multi": ([PP, I, P, S, S, P, I, P, S, S, S, S], I),
         "hrs_encode_batch_host_multi": ([PP, I, P, S, S, S, S], I),
         "hrs_device_count": ([], I),

@@ -221,6 +221,7 @@ void hrs_destroy(hrs_codec* c) {
   for (hipStream_t s : {c->hbatch_in, c->hbatch_out})
     if (s) (void)hipStreamDestroy(s);
   if (c->scrub_reports) (void)hipFree(c->scrub_reports);  // the host-batch streams have drained above
+  if (c->hbatch_crc) (void)hipFree(c->hbatch_crc);
   for (auto& b : c->batch) {
     if (b.done) {
       (void)hipEventSynchronize(b.done);

@@ -2,7 +2,8 @@
 // per stripe, plans uploaded through pinned slots, one batch launch) and the
 // host-memory batch pipelines (hrs_decode_batch_host / hrs_encode_batch_host:
 // chunks of stripes through a ring of device slots, H2D of exactly the rows
-// read, D2H of exactly the rows written).
+// read, D2H of exactly the rows written), each with its block-CRC-32 form
+// (hrs_decode_batch_crc_dev, hrs_decode_batch_host_crc, hrs_encode_batch_host_crc).
 #include <hip/hip_runtime.h>
 #include <hsa/hsa.h>
 #include <hsa/hsa_ext_amd.h>
@@ -18,6 +19,7 @@
 
 #include "../../include/hrs.h"
 #include "hrs_codec.hpp"
+#include "hrs_crc.hpp"
 #include "hrs_host.hpp"
 #include "hrs_internal.hpp"
 #include "hrs_launch.hpp"
@@ -145,6 +147,94 @@ hrs_status launch_batch(hrs_codec* c, const BatchPlanSet& ps, const hrs::BatchPl
     if (a.nwin == 0) c->last_kernel = hrs::last_kernel();  // the call's only kernel
   }
   return HRS_OK;
+}
+
+// launch_batch + the CRC-32 of every repaired cell of stripes [s0, s0 + ns):
+// crc_out[i * max_erased + t] (device; i counts from s0) continues
+// crc_in[...] (NULL = fresh) over output t of stripe s0 + i, and over no bytes
+// for t past the stripe's losses. dplans / dpat are always uploaded (the fold
+// reads every stripe's loss count from them, the per-stripe fallback's too).
+// raw: crc_raw_bytes_for(len, ns, max_erased) bytes of scratch.
+// One pass (batch_decode_crc_kernel) for aligned whole-window batches of the
+// one-pattern fused kernel's shapes; else launch_batch, the CRC window pass
+// over the outputs (rows past a stripe's losses lie inside `out` and are read;
+// the fold discards them) and the same fold.
+hrs_status launch_batch_crc(hrs_codec* c, const BatchPlanSet& ps, const hrs::BatchPlan* dplans, const int32_t* dpat,
+                            const uint8_t* stripes, size_t row_stride, size_t stripe_stride, uint8_t* out,
+                            size_t out_row_stride, size_t out_stripe_stride, size_t len, size_t s0, size_t ns,
+                            int max_erased, const uint32_t* crc_in, uint32_t* crc_out, hipStream_t hs, uint32_t* raw) {
+  const BatchCrcMask mask{dplans, dpat + s0, max_erased};
+  if (ps.max_nout == 0)  // nothing lost anywhere: every CRC continues over no bytes
+    return batch_crc_fold(c, len, ns, mask, crc_in, crc_out, hs, raw, hrs::kCrcWindow);
+  const bool one_pass = ps.fused && (c->kernel_mode == 0 || c->kernel_mode == 3) && len % hrs::kWindowBytes == 0 &&
+                        aligned16(stripes) && aligned16(out) && row_stride % 16 == 0 && stripe_stride % 16 == 0 &&
+                        out_row_stride % 16 == 0 && out_stripe_stride % 16 == 0 && ps.max_nout <= 4 &&
+                        ps.max_nin <= (ps.max_nout == 4 ? 8 : 12);
+  if (one_pass) {
+    hrs_status st = crc_window_tables(c);
+    if (st != HRS_OK) return st;
+    hrs::BatchCrcArgs d{};
+    d.b.base = stripes;
+    d.b.out = out;
+    d.b.row_stride = row_stride;
+    d.b.stripe_stride = stripe_stride;
+    d.b.out_row_stride = out_row_stride;
+    d.b.out_stripe_stride = out_stripe_stride;
+    d.b.len = len;
+    d.b.nwin = len / hrs::kWindowBytes;
+    d.b.ntasks = d.b.nwin * ns;
+    d.b.plans = dplans;
+    d.b.pat = dpat + s0;
+    d.raw = raw;
+    d.tables = c->crc_tables_a;
+    d.rows_per_stripe = max_erased;
+    hipError_t e = hrs::launch_batch_decode_crc(d, ps.max_nout, ps.max_nin, hrs::device_cu_count(), hs);
+    if (e != hipSuccess) return hip_fail(c, e, "batch decode+crc launch");
+    c->last_kernel = hrs::last_kernel();
+    return batch_crc_fold(c, len, ns, mask, crc_in, crc_out, hs, raw, hrs::kWindowBytes);
+  }
+  hrs_status st = launch_batch(c, ps, dplans, dpat, stripes, row_stride, stripe_stride, out, out_row_stride,
+                               out_stripe_stride, len, s0, ns, hs);
+  if (st != HRS_OK) return st;
+  const uint8_t* rows[hrs::kMaxOut];
+  size_t strides[hrs::kMaxOut];
+  for (int t = 0; t < ps.max_nout; ++t) {
+    rows[t] = out + static_cast<size_t>(t) * out_row_stride;
+    strides[t] = out_stripe_stride;
+  }
+  st = crc_windows(c, rows, strides, ps.max_nout, max_erased, len, ns, hs, raw);
+  if (st != HRS_OK) return st;
+  return batch_crc_fold(c, len, ns, mask, crc_in, crc_out, hs, raw, hrs::kCrcWindow);
+}
+
+// crc_out may be crc_in itself; any other overlap of the two n-word arrays is refused.
+bool crc_arrays_apart(const uint32_t* crc_in, const uint32_t* crc_out, size_t n) {
+  if (!crc_in || crc_in == crc_out) return true;
+  const uintptr_t a = reinterpret_cast<uintptr_t>(crc_in), b = reinterpret_cast<uintptr_t>(crc_out);
+  return a + n * 4 <= b || b + n * 4 <= a;
+}
+
+// The device CRC buffer of a host batch (n words), filled from crc_in (host).
+hrs_status hbatch_crc_buffer(hrs_codec* c, size_t n, const uint32_t* crc_in) {
+  const size_t bytes = n * sizeof(uint32_t);
+  if (c->hbatch_crc_bytes < bytes) {  // every earlier batch has completed: the calls are synchronous
+    if (c->hbatch_crc) (void)hipFree(c->hbatch_crc);
+    c->hbatch_crc = nullptr;
+    c->hbatch_crc_bytes = 0;
+    const hipError_t e = hipMalloc(&c->hbatch_crc, bytes);
+    if (e != hipSuccess) return fail(c, HRS_ENOMEM, "hipMalloc(%zu): %s", bytes, hipGetErrorString(e));
+    c->hbatch_crc_bytes = bytes;
+  }
+  if (crc_in) {
+    const hipError_t e = hipMemcpy(c->hbatch_crc, crc_in, bytes, hipMemcpyHostToDevice);
+    if (e != hipSuccess) return hip_fail(c, e, "hipMemcpy crc_in");
+  }
+  return HRS_OK;
+}
+
+hrs_status hbatch_crc_fetch(hrs_codec* c, size_t n, uint32_t* crc_out) {
+  const hipError_t e = hipMemcpy(crc_out, c->hbatch_crc, n * sizeof(uint32_t), hipMemcpyDeviceToHost);
+  return e == hipSuccess ? HRS_OK : hip_fail(c, e, "hipMemcpy crc_out");
 }
 
 // Uploads plans + pattern indices through the next of the handle's two
@@ -560,21 +650,31 @@ hrs_status drain_hbatch(hrs_codec* c, hrs_status st) {
 // hrs_decode_batch_host with pinned stripes and outputs: one batch launch
 // whose kernels read the survivors and write the repaired cells across the
 // host link directly (zero copy). The plans go up first on slot 0's stream;
-// the call returns once the launch has completed.
+// the call returns once the launch has completed. dcrc_out (device, with
+// dcrc_in; hrs_decode_batch_host_crc): launch_batch_crc over max_erased rows.
 hrs_status zero_copy_batch(hrs_codec* c, const BatchPlanSet& ps, const uint8_t* ds, size_t row_stride,
                            size_t stripe_stride, uint8_t* dout, size_t out_row_stride, size_t out_stripe_stride,
-                           size_t len, size_t nstripes) {
+                           size_t len, size_t nstripes, int max_erased = 0, const uint32_t* dcrc_in = nullptr,
+                           uint32_t* dcrc_out = nullptr) {
   hrs_status st = hbatch_slot(c, 0, 0, 0);
   if (st != HRS_OK) return st;
   const hipStream_t hs = c->hbatch[0].stream;
   hrs_codec::BatchSlot* bsl = nullptr;
   const hrs::BatchPlan* dplans = nullptr;
   const int32_t* dpat = nullptr;
-  if (ps.fused) {
+  if (ps.fused || dcrc_out) {
     st = upload_batch_plans(c, ps, hs, &bsl, &dplans, &dpat);
     if (st != HRS_OK) return st;
   }
-  {
+  if (dcrc_out) {
+    st = crc_scratch(c, crc_raw_bytes_for(len, nstripes, max_erased), hs);
+    if (st != HRS_OK) return st;
+    hrs::GridCap cap(zero_copy_blocks());
+    st = crc_scratch_release(c, hs,
+                             launch_batch_crc(c, ps, dplans, dpat, ds, row_stride, stripe_stride, dout, out_row_stride,
+                                              out_stripe_stride, len, 0, nstripes, max_erased, dcrc_in, dcrc_out, hs,
+                                              c->crc_raw));
+  } else {
     hrs::GridCap cap(zero_copy_blocks());
     st = launch_batch(c, ps, dplans, dpat, ds, row_stride, stripe_stride, dout, out_row_stride, out_stripe_stride,
                       len, 0, nstripes, hs);
@@ -666,7 +766,8 @@ const char* batch_path(bool pinned) {
 
 hrs_status decode_batch_host_impl(hrs_codec* c, const uint8_t* stripes, size_t row_stride, size_t stripe_stride,
                                   const int* erased, int max_erased, uint8_t* out, size_t out_row_stride,
-                                  size_t out_stripe_stride, size_t len, size_t nstripes) {
+                                  size_t out_stripe_stride, size_t len, size_t nstripes,
+                                  const uint32_t* crc_in = nullptr, uint32_t* crc_out = nullptr) {
   if (!c) return HRS_EINVAL;
   if (!stripes || !out || max_erased < 0 || max_erased > hrs::kMaxOut || (max_erased > 0 && !erased))
     return fail(c, HRS_EINVAL, "bad batch decode arguments (max_erased must be in [0, %d])", hrs::kMaxOut);
@@ -675,14 +776,32 @@ hrs_status decode_batch_host_impl(hrs_codec* c, const uint8_t* stripes, size_t r
   BatchPlanSet ps;
   hrs_status st = build_batch_plans(c, erased, max_erased, nstripes, ps);
   if (st != HRS_OK) return st;
-  if (ps.max_nout == 0) return HRS_OK;
+  if (ps.max_nout == 0 && !crc_out) return HRS_OK;
   DeviceGuard g(c->device);
   if (!g.ok) return fail(c, HRS_EDEVICE, "cannot select HIP device %d", c->device);
+  // hrs_decode_batch_host_crc (crc_out != NULL; HOST arrays): the CRCs
+  // accumulate in the handle's device buffer, filled from crc_in, written by
+  // the slot streams' folds, and come back in one copy after the last chunk
+  const size_t ncrc = nstripes * static_cast<size_t>(max_erased);
+  const uint32_t* dcrc_in = nullptr;
+  if (crc_out) {
+    if (ps.max_nout == 0) {  // nothing lost anywhere: every CRC continues over no bytes
+      if (crc_in) std::memmove(crc_out, crc_in, ncrc * sizeof(uint32_t));
+      else std::memset(crc_out, 0, ncrc * sizeof(uint32_t));
+      return HRS_OK;
+    }
+    st = hbatch_crc_buffer(c, ncrc, crc_in);
+    if (st != HRS_OK) return st;
+    if (crc_in) dcrc_in = c->hbatch_crc;
+  }
+  uint32_t* const dcrc = crc_out ? c->hbatch_crc : nullptr;
   uint8_t *zs = nullptr, *zo = nullptr;
   if (zero_copy_on() && host_device_ptr(stripes, batch_span(nstripes, stripe_stride, c->n, row_stride, len), &zs) &&
-      host_device_ptr(out, batch_span(nstripes, out_stripe_stride, max_erased, out_row_stride, len), &zo))
-    return drain_hbatch(c, zero_copy_batch(c, ps, zs, row_stride, stripe_stride, zo, out_row_stride,
-                                           out_stripe_stride, len, nstripes));
+      host_device_ptr(out, batch_span(nstripes, out_stripe_stride, max_erased, out_row_stride, len), &zo)) {
+    st = drain_hbatch(c, zero_copy_batch(c, ps, zs, row_stride, stripe_stride, zo, out_row_stride, out_stripe_stride,
+                                         len, nstripes, max_erased, dcrc_in, dcrc));
+    return st == HRS_OK && crc_out ? hbatch_crc_fetch(c, ncrc, crc_out) : st;
+  }
   // rows each pattern reads: its live locations (every location for the
   // per-stripe fallback of wide patterns, which reads what its matrix needs)
   std::vector<std::vector<RowRun>> pruns(ps.plans.size());
@@ -708,7 +827,7 @@ hrs_status decode_batch_host_impl(hrs_codec* c, const uint8_t* stripes, size_t r
   const int32_t* dpat = nullptr;
   st = hbatch_slot(c, 0, 0, 0);
   if (st != HRS_OK) return st;
-  if (ps.fused) {
+  if (ps.fused || crc_out) {
     st = upload_batch_plans(c, ps, c->hbatch[0].stream, &bsl, &dplans, &dpat);
     if (st != HRS_OK) return st;
     hipError_t e = hipEventRecord(bsl->done, c->hbatch[0].stream);
@@ -725,7 +844,18 @@ hrs_status decode_batch_host_impl(hrs_codec* c, const uint8_t* stripes, size_t r
   auto writes = [&](size_t s) -> int { return ps.plans[ps.pat[s]].nout; };
   auto compute = [&](hipStream_t hs, size_t s0, size_t ns, uint8_t* dimg, size_t img_stripe, size_t dpitch,
                      uint8_t* dout, size_t out_stripe_dev) -> hrs_status {
-    return launch_batch(c, ps, dplans, dpat, dimg, dpitch, img_stripe, dout, dpitch, out_stripe_dev, len, s0, ns, hs);
+    if (!dcrc)
+      return launch_batch(c, ps, dplans, dpat, dimg, dpitch, img_stripe, dout, dpitch, out_stripe_dev, len, s0, ns, hs);
+    // the slots share the handle's raw-CRC scratch: crc_scratch chains its
+    // uses by an event, so the slots' CRC kernels run one after another
+    // (each fills the chip); their copies still overlap them
+    hrs_status cs = crc_scratch(c, crc_raw_bytes_for(len, ns, max_erased), hs);
+    if (cs != HRS_OK) return cs;
+    const size_t at = s0 * static_cast<size_t>(max_erased);
+    return crc_scratch_release(c, hs,
+                               launch_batch_crc(c, ps, dplans, dpat, dimg, dpitch, img_stripe, dout, dpitch,
+                                                out_stripe_dev, len, s0, ns, max_erased,
+                                                dcrc_in ? dcrc_in + at : nullptr, dcrc + at, hs, c->crc_raw));
   };
   st = host_batch(c, stripes, row_stride, stripe_stride, c->n, out, out_row_stride, out_stripe_stride, ps.max_nout,
                   len, nstripes, reads, compute, writes);
@@ -733,17 +863,38 @@ hrs_status decode_batch_host_impl(hrs_codec* c, const uint8_t* stripes, size_t r
     hipError_t e = hipEventRecord(bsl->done, c->hbatch[0].stream);
     if (e != hipSuccess) st = hip_fail(c, e, "hipEventRecord");
   }
-  return drain_hbatch(c, st);
+  st = drain_hbatch(c, st);
+  return st == HRS_OK && crc_out ? hbatch_crc_fetch(c, ncrc, crc_out) : st;
 }
 
+// crc_out != NULL (hrs_encode_batch_host_crc; HOST arrays of nstripes * n
+// words): encode_crc_impl instead of run_apply, the CRCs through the handle's
+// device buffer as in decode_batch_host_impl.
 hrs_status encode_batch_host_impl(hrs_codec* c, uint8_t* stripes, size_t row_stride, size_t stripe_stride, size_t len,
-                                  size_t nstripes) {
+                                  size_t nstripes, const uint32_t* crc_in = nullptr, uint32_t* crc_out = nullptr) {
   if (!c) return HRS_EINVAL;
   if (!stripes) return fail(c, HRS_EINVAL, "stripes is NULL");
   if (nstripes == 0 || len == 0) return HRS_OK;
   DeviceGuard g(c->device);
   if (!g.ok) return fail(c, HRS_EDEVICE, "cannot select HIP device %d", c->device);
   const int k = c->k, p = c->p;
+  const size_t n = static_cast<size_t>(c->n), ncrc = nstripes * n;
+  const uint32_t* dcrc_in = nullptr;
+  if (crc_out) {
+    hrs_status st = hbatch_crc_buffer(c, ncrc, crc_in);
+    if (st != HRS_OK) return st;
+    if (crc_in) dcrc_in = c->hbatch_crc;
+  }
+  uint32_t* const dcrc = crc_out ? c->hbatch_crc : nullptr;
+  // encode + CRC of stripes [s0, s0 + ns) on hs, the raw scratch chained across the slot streams
+  auto encode_crc = [&](const uint8_t* const* in, size_t in_stride, uint8_t* const* outp, size_t out_stride, size_t s0,
+                        size_t ns, hipStream_t hs) -> hrs_status {
+    hrs_status cs = crc_scratch(c, crc_raw_bytes_for(len, ns, c->n), hs);
+    if (cs != HRS_OK) return cs;
+    return crc_scratch_release(c, hs,
+                               encode_crc_impl(c, in, in_stride, outp, out_stride, len, ns,
+                                               dcrc_in ? dcrc_in + s0 * n : nullptr, dcrc + s0 * n, hs, c->crc_raw));
+  };
   uint8_t* zs = nullptr;
   if (zero_copy_on() && host_device_ptr(stripes, batch_span(nstripes, stripe_stride, c->n, row_stride, len), &zs)) {
     // runtime-pinned: the kernel works on the caller's stripes in place
@@ -756,30 +907,34 @@ hrs_status encode_batch_host_impl(hrs_codec* c, uint8_t* stripes, size_t row_str
     for (int r = 0; r < p; ++r) outp[r] = zs + static_cast<size_t>(r) * row_stride;
     {
       hrs::GridCap cap(zero_copy_blocks());
-      st = run_apply(c, c->g.data(), p, k, in.data(), stripe_stride, outp.data(), stripe_stride, len, nstripes, hs,
-                     static_encode_family(c));
+      st = dcrc ? encode_crc(in.data(), stripe_stride, outp.data(), stripe_stride, 0, nstripes, hs)
+                : run_apply(c, c->g.data(), p, k, in.data(), stripe_stride, outp.data(), stripe_stride, len, nstripes,
+                            hs, static_encode_family(c));
     }
     if (st == HRS_OK) {
       const hipError_t e = hipStreamSynchronize(hs);
       if (e != hipSuccess) st = hip_fail(c, e, "hipStreamSynchronize");
     }
-    return drain_hbatch(c, st);
+    st = drain_hbatch(c, st);
+    return st == HRS_OK && crc_out ? hbatch_crc_fetch(c, ncrc, crc_out) : st;
   }
   const std::vector<RowRun> data_rows{{p, k}};  // hops locations p..n-1: one run
   auto reads = [&](size_t) -> const std::vector<RowRun>& { return data_rows; };
   auto writes = [&](size_t) -> int { return p; };
   std::vector<const uint8_t*> in(k);
   std::vector<uint8_t*> outp(p);
-  auto compute = [&](hipStream_t hs, size_t, size_t ns, uint8_t* dimg, size_t img_stripe, size_t dpitch,
+  auto compute = [&](hipStream_t hs, size_t s0, size_t ns, uint8_t* dimg, size_t img_stripe, size_t dpitch,
                      uint8_t* dout, size_t out_stripe_dev) -> hrs_status {
     for (int i = 0; i < k; ++i) in[i] = dimg + static_cast<size_t>(p + i) * dpitch;
     for (int r = 0; r < p; ++r) outp[r] = dout + static_cast<size_t>(r) * dpitch;
+    if (dcrc) return encode_crc(in.data(), img_stripe, outp.data(), out_stripe_dev, s0, ns, hs);
     return run_apply(c, c->g.data(), p, k, in.data(), img_stripe, outp.data(), out_stripe_dev, len, ns, hs,
                      static_encode_family(c));
   };
   // parity rows 0..p-1 of each stripe are written in place
-  return drain_hbatch(c, host_batch(c, stripes, row_stride, stripe_stride, c->n, stripes, row_stride, stripe_stride,
-                                    p, len, nstripes, reads, compute, writes));
+  const hrs_status st = drain_hbatch(c, host_batch(c, stripes, row_stride, stripe_stride, c->n, stripes, row_stride,
+                                                   stripe_stride, p, len, nstripes, reads, compute, writes));
+  return st == HRS_OK && crc_out ? hbatch_crc_fetch(c, ncrc, crc_out) : st;
 }
 
 // hrs_scrub_batch_host: every stripe's n rows are its reads, there are no
@@ -956,6 +1111,82 @@ hrs_status hrs_encode_batch_host(hrs_codec* c, uint8_t* stripes, size_t row_stri
   if (!stripes) return fail(c, HRS_EINVAL, "stripes is NULL");
   if (nstripes == 0 || len == 0) return HRS_OK;
   const hrs_status st = encode_batch_host_impl(c, stripes, row_stride, stripe_stride, len, nstripes);
+  if (st == HRS_OK) {
+    DeviceGuard g(c->device);
+    c->last_host_path =
+        batch_path(g.ok && runtime_pinned(stripes, batch_span(nstripes, stripe_stride, c->n, row_stride, len)));
+  }
+  return st;
+}
+
+hrs_status hrs_decode_batch_crc_dev(hrs_codec* c, const uint8_t* stripes, size_t row_stride, size_t stripe_stride,
+                                    const int* erased, int max_erased, uint8_t* out, size_t out_row_stride,
+                                    size_t out_stripe_stride, size_t len, size_t nstripes, const uint32_t* crc_in,
+                                    uint32_t* crc_out, void* stream) {
+  if (!c) return HRS_EINVAL;
+  if (!stripes || !out || max_erased < 0 || max_erased > hrs::kMaxOut || (max_erased > 0 && !erased))
+    return fail(c, HRS_EINVAL, "bad batch decode arguments (max_erased must be in [0, %d])", hrs::kMaxOut);
+  if (nstripes == 0 || len == 0 || max_erased == 0) return HRS_OK;
+  if (nstripes > 0x7fffffffu) return fail(c, HRS_EINVAL, "too many stripes");
+  if (!crc_out) return fail(c, HRS_EINVAL, "crc_out is NULL");
+  if (!crc_arrays_apart(crc_in, crc_out, nstripes * static_cast<size_t>(max_erased)))
+    return fail(c, HRS_EINVAL, "crc_in and crc_out overlap (crc_out may only be crc_in itself)");
+  BatchPlanSet ps;
+  hrs_status st = build_batch_plans(c, erased, max_erased, nstripes, ps);
+  if (st != HRS_OK) return st;
+  DeviceGuard g(c->device);
+  if (!g.ok) return fail(c, HRS_EDEVICE, "cannot select HIP device %d", c->device);
+  hipStream_t hs = static_cast<hipStream_t>(stream);
+  hrs_codec::BatchSlot* sl = nullptr;
+  const hrs::BatchPlan* dplans = nullptr;
+  const int32_t* dpat = nullptr;
+  st = upload_batch_plans(c, ps, hs, &sl, &dplans, &dpat);
+  if (st != HRS_OK) return st;
+  st = crc_scratch(c, crc_raw_bytes_for(len, nstripes, max_erased), hs);
+  if (st != HRS_OK) return st;
+  st = crc_scratch_release(c, hs,
+                           launch_batch_crc(c, ps, dplans, dpat, stripes, row_stride, stripe_stride, out,
+                                            out_row_stride, out_stripe_stride, len, 0, nstripes, max_erased, crc_in,
+                                            crc_out, hs, c->crc_raw));
+  if (st != HRS_OK) return st;
+  hipError_t e = hipEventRecord(sl->done, hs);
+  if (e != hipSuccess) return hip_fail(c, e, "hipEventRecord");
+  sl->pending = true;
+  return HRS_OK;
+}
+
+hrs_status hrs_decode_batch_host_crc(hrs_codec* c, const uint8_t* stripes, size_t row_stride, size_t stripe_stride,
+                                     const int* erased, int max_erased, uint8_t* out, size_t out_row_stride,
+                                     size_t out_stripe_stride, size_t len, size_t nstripes, const uint32_t* crc_in,
+                                     uint32_t* crc_out) {
+  if (!c) return HRS_EINVAL;
+  if (!stripes || !out || max_erased < 0 || max_erased > hrs::kMaxOut || (max_erased > 0 && !erased))
+    return fail(c, HRS_EINVAL, "bad batch decode arguments (max_erased must be in [0, %d])", hrs::kMaxOut);
+  if (nstripes == 0 || len == 0 || max_erased == 0) return HRS_OK;
+  if (nstripes > 0x7fffffffu) return fail(c, HRS_EINVAL, "too many stripes");
+  if (!crc_out) return fail(c, HRS_EINVAL, "crc_out is NULL");
+  if (!crc_arrays_apart(crc_in, crc_out, nstripes * static_cast<size_t>(max_erased)))
+    return fail(c, HRS_EINVAL, "crc_in and crc_out overlap (crc_out may only be crc_in itself)");
+  const hrs_status st = decode_batch_host_impl(c, stripes, row_stride, stripe_stride, erased, max_erased, out,
+                                               out_row_stride, out_stripe_stride, len, nstripes, crc_in, crc_out);
+  if (st == HRS_OK) {
+    DeviceGuard g(c->device);
+    c->last_host_path =
+        batch_path(g.ok && runtime_pinned(stripes, batch_span(nstripes, stripe_stride, c->n, row_stride, len)) &&
+                   runtime_pinned(out, batch_span(nstripes, out_stripe_stride, max_erased, out_row_stride, len)));
+  }
+  return st;
+}
+
+hrs_status hrs_encode_batch_host_crc(hrs_codec* c, uint8_t* stripes, size_t row_stride, size_t stripe_stride,
+                                     size_t len, size_t nstripes, const uint32_t* crc_in, uint32_t* crc_out) {
+  if (!c) return HRS_EINVAL;
+  if (!stripes) return fail(c, HRS_EINVAL, "stripes is NULL");
+  if (nstripes == 0 || len == 0) return HRS_OK;
+  if (!crc_out) return fail(c, HRS_EINVAL, "crc_out is NULL");
+  if (!crc_arrays_apart(crc_in, crc_out, nstripes * static_cast<size_t>(c->n)))
+    return fail(c, HRS_EINVAL, "crc_in and crc_out overlap (crc_out may only be crc_in itself)");
+  const hrs_status st = encode_batch_host_impl(c, stripes, row_stride, stripe_stride, len, nstripes, crc_in, crc_out);
   if (st == HRS_OK) {
     DeviceGuard g(c->device);
     c->last_host_path =

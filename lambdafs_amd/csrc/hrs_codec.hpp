@@ -107,6 +107,10 @@ struct hrs_codec {
   // in one copy when the batch has run
   uint32_t* scrub_reports = nullptr;
   size_t scrub_reports_bytes = 0;
+  // hrs_*_batch_host_crc: the CRCs accumulate here (device; filled from
+  // crc_in first) and come back in one copy when the batch has run
+  uint32_t* hbatch_crc = nullptr;
+  size_t hbatch_crc_bytes = 0;
   hipStream_t hbatch_in = nullptr;   // H2D of every host-batch slot
   hipStream_t hbatch_out = nullptr;  // D2H of every host-batch slot
   // asynchronous host-buffer calls (hrs_*_submit / hrs_collect): a ring of
@@ -220,6 +224,24 @@ hrs_status run_apply(hrs_codec* c, const uint8_t* m, int nout, int nin, const ui
 size_t crc_raw_bytes_for(size_t len, size_t nstripes, int nrows);
 hrs_status run_crc(hrs_codec* c, const uint8_t* const* rows, const size_t* strides, int nrows, size_t len,
                    size_t nstripes, const uint32_t* crc_in, uint32_t* crc_out, hipStream_t s, uint32_t* raw);
+// The handle's raw-CRC scratch (c->crc_raw, at least `bytes`) for a call on
+// stream s, its uses chained by an event across streams; release records it.
+hrs_status crc_scratch(hrs_codec* c, size_t bytes, hipStream_t s);
+hrs_status crc_scratch_release(hrs_codec* c, hipStream_t s, hrs_status st);
+hrs_status crc_window_tables(hrs_codec* c);  // c->crc_tables_a, uploaded once
+// run_crc's window pass alone, raw rows laid out for a fold over nrows_total rows.
+hrs_status crc_windows(hrs_codec* c, const uint8_t* const* rows, const size_t* strides, int nrows, int nrows_total,
+                       size_t len, size_t nstripes, hipStream_t s, uint32_t* raw);
+// The fold of a repair batch (windows of `win` bytes): output t of stripe s
+// past the stripe's losses (t >= plans[pat[s]].nout; device tables) yields
+// crc_in (0 when NULL) without reading raw. crc_out[s * rows_per_stripe + t].
+struct BatchCrcMask {
+  const hrs::BatchPlan* plans;
+  const int32_t* pat;
+  int rows_per_stripe;
+};
+hrs_status batch_crc_fold(hrs_codec* c, size_t len, size_t nstripes, const BatchCrcMask& mask, const uint32_t* crc_in,
+                          uint32_t* crc_out, hipStream_t s, uint32_t* raw, uint64_t win);
 // host_fold_win != NULL: when the fused one-pass kernel runs, no fold is
 // launched; the raw window CRCs stay in `raw` (layout [stripe][row][window])
 // and *host_fold_win receives the window size for the caller's host fold

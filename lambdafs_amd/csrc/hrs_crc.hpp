@@ -111,4 +111,32 @@ struct DecodeCrcArgs {
 };
 hipError_t launch_decode_crc(const DecodeCrcArgs& d, int cus, hipStream_t s, bool* handled);
 
+// Fused heterogeneous repair batch + CRC-32 (hrs_batch_crc.hip): the batch
+// launch `b` (whole 2 KiB windows; b.ntasks = b.nwin * stripes) with the raw
+// CRC of every PRESENT output's window in
+// raw[(stripe * rows_per_stripe + output) * nwin + window]; rows_per_stripe is
+// the caller's max_erased, so (stripe, output) indexes crc_out. Outputs past a
+// stripe's losses get no raw word. Shapes: max_nout 1-4, max_nin <= 12 (<= 8
+// at 4 outputs); anything else is hipErrorInvalidValue (the host checks first).
+struct BatchCrcArgs {
+  BatchArgs b;
+  uint32_t* raw;
+  const uint32_t* tables;  // kCrcLdsWordsA words (device)
+  int rows_per_stripe;
+  int pad_;
+};
+hipError_t launch_batch_decode_crc(const BatchCrcArgs& d, int max_nout, int max_nin, int cus, hipStream_t s);
+
+// The fold of a batch's raw window CRCs: f as for launch_crc_fold with
+// f.nsr = stripes * rows_per_stripe; pair (s, t) with t >= plans[pat[s]].nout
+// yields crc_in (0 when NULL) without reading raw, so crc_out may alias crc_in.
+struct BatchCrcFoldArgs {
+  CrcFoldArgs f;
+  const BatchPlan* plans;  // device table
+  const int32_t* pat;      // device: pattern index of each stripe
+  int rows_per_stripe;
+  int pad_;
+};
+hipError_t launch_batch_crc_fold(const BatchCrcFoldArgs& b, int cus, hipStream_t s);
+
 }  // namespace hrs

@@ -336,8 +336,10 @@ hrs_status crc_scratch_release(hrs_codec* c, hipStream_t s, hrs_status st) {
 
 // Folds the raw window CRCs (windows of `win` bytes) of nsr (stripe, row)
 // pairs into CRC32 values.
+// mask (batches): pair (stripe, t) of rows_per_stripe with
+// t >= plans[pat[stripe]].nout has no raw words and yields crc_in (0 when NULL).
 hrs_status crc_fold(hrs_codec* c, size_t len, uint64_t nsr, const uint32_t* crc_in, uint32_t* crc_out, hipStream_t s,
-                    uint32_t* raw, uint64_t win = hrs::kCrcWindow) {
+                    uint32_t* raw, uint64_t win = hrs::kCrcWindow, const BatchCrcMask* mask = nullptr) {
   hrs_codec::FoldTables* ft = nullptr;
   hrs_status st = crc_fold_tables(c, len, win, &ft);
   if (st != HRS_OK) return st;
@@ -351,7 +353,17 @@ hrs_status crc_fold(hrs_codec* c, size_t len, uint64_t nsr, const uint32_t* crc_
   f.tables = fold;
   f.crc_in = crc_in;
   f.crc_out = crc_out;
-  hipError_t e = hrs::launch_crc_fold(f, hrs::device_cu_count(), s);
+  hipError_t e;
+  if (mask) {
+    hrs::BatchCrcFoldArgs b{};
+    b.f = f;
+    b.plans = mask->plans;
+    b.pat = mask->pat;
+    b.rows_per_stripe = mask->rows_per_stripe;
+    e = hrs::launch_batch_crc_fold(b, hrs::device_cu_count(), s);
+  } else {
+    e = hrs::launch_crc_fold(f, hrs::device_cu_count(), s);
+  }
   if (e != hipSuccess) return hip_fail(c, e, "crc fold launch");
   return fold_tables_used(c, ft, s);  // the tables may be freed once this fold has run
 }
@@ -385,6 +397,16 @@ size_t crc_raw_bytes_for(size_t len, size_t nstripes, int nrows) {
 // crc_out[s * nrows + r].
 hrs_status run_crc(hrs_codec* c, const uint8_t* const* rows, const size_t* strides, int nrows, size_t len,
                    size_t nstripes, const uint32_t* crc_in, uint32_t* crc_out, hipStream_t s, uint32_t* raw) {
+  hrs_status st = crc_windows(c, rows, strides, nrows, nrows, len, nstripes, s, raw);
+  if (st != HRS_OK) return st;
+  return crc_fold(c, len, nstripes * nrows, crc_in, crc_out, s, raw);
+}
+
+// The window pass alone: raw window CRCs of rows 0..nrows-1 of every stripe
+// in raw[(stripe * nrows_total + row) * windows + window] (nrows_total >= nrows:
+// the row count of the fold that follows).
+hrs_status crc_windows(hrs_codec* c, const uint8_t* const* rows, const size_t* strides, int nrows, int nrows_total,
+                       size_t len, size_t nstripes, hipStream_t s, uint32_t* raw) {
   hrs_status st = crc_window_tables(c);
   if (st != HRS_OK) return st;
   const uint64_t nwin = len / hrs::kCrcWindow, tail = len % hrs::kCrcWindow;
@@ -401,7 +423,7 @@ hrs_status run_crc(hrs_codec* c, const uint8_t* const* rows, const size_t* strid
         a.stride[r] = strides[r0 + r];
       }
       a.row0 = r0;
-      a.nrows_total = nrows;
+      a.nrows_total = nrows_total;
       a.len = len;
       a.nwin = nwin;
       a.tail = tail;
@@ -412,7 +434,12 @@ hrs_status run_crc(hrs_codec* c, const uint8_t* const* rows, const size_t* strid
       if (e != hipSuccess) return hip_fail(c, e, "crc window launch");
     }
   }
-  return crc_fold(c, len, nstripes * nrows, crc_in, crc_out, s, raw);
+  return HRS_OK;
+}
+
+hrs_status batch_crc_fold(hrs_codec* c, size_t len, size_t nstripes, const BatchCrcMask& mask, const uint32_t* crc_in,
+                          uint32_t* crc_out, hipStream_t s, uint32_t* raw, uint64_t win) {
+  return crc_fold(c, len, nstripes * static_cast<uint64_t>(mask.rows_per_stripe), crc_in, crc_out, s, raw, win, &mask);
 }
 
 // Slicing-table copies the fused kernel's lanes spread over: 32 (each lane of

@@ -165,6 +165,52 @@ def decode_batch(code, stripes, erased, out):
         out.data_ptr(), out.stride(1), out.stride(0), L, S, _stream(stripes)))
 
 
+def decode_batch_crc(code, stripes, erased, out, crc_in=None, crc_out=None):
+    """decode_batch plus the CRC-32 (java.util.zip.CRC32) of every repaired cell
+    in one pass (hrs_decode_batch_crc_dev): returns an int32 tensor [S, E] of
+    the uint32 CRC bits, entry [s, t] for output t of stripe s. crc_in (same
+    layout) continues running CRCs across successive cells; an entry past its
+    stripe's losses continues over no bytes and keeps its crc_in value (0
+    without crc_in). crc_out: the tensor to fill and return (it may be crc_in
+    itself) instead of a new one."""
+    torch = _lib.torch
+    n = code.stripeSize() + code.paritySize()
+    if stripes.dim() != 3 or stripes.shape[1] != n or stripes.stride(2) != 1:
+        raise ValueError(f"stripes must be [S, {n}, L] with unit byte stride")
+    e = np.ascontiguousarray(np.asarray(erased, dtype=np.int32))
+    S, L = stripes.shape[0], stripes.shape[2]
+    if e.ndim != 2 or e.shape[0] != S:
+        raise ValueError("erased must be [S, E]")
+    if out.dim() != 3 or tuple(out.shape) != (S, e.shape[1], L) or out.stride(2) != 1 or out.device != stripes.device:
+        raise ValueError("out must be [S, E, L] on the stripes' device")
+    for name, t in (("crc_in", crc_in), ("crc_out", crc_out)):
+        if t is not None and (tuple(t.shape) != (S, e.shape[1]) or t.dtype != torch.int32 or not t.is_contiguous()
+                              or t.device != stripes.device):
+            raise ValueError(f"{name} must be a contiguous int32 tensor [S, {e.shape[1]}] on the stripes' device")
+    crc = crc_out if crc_out is not None else torch.empty((S, e.shape[1]), dtype=torch.int32, device=stripes.device)
+    if L == 0 and crc is not crc_in:  # the call touches nothing: every CRC continues over no bytes
+        crc.zero_() if crc_in is None else crc.copy_(crc_in)
+    code._check(_lib.lib().hrs_decode_batch_crc_dev(
+        code._handle(), stripes.data_ptr(), stripes.stride(1), stripes.stride(0), e.ctypes.data, e.shape[1],
+        out.data_ptr(), out.stride(1), out.stride(0), L, S, None if crc_in is None else crc_in.data_ptr(),
+        crc.data_ptr(), _stream(stripes)))
+    return crc
+
+
+def _host_crcs(shape, L, crc_in, crc_out):
+    """(crc_in pointer or None, the uint32 result array) of a host batch of L-byte cells."""
+    for name, a in (("crc_in", crc_in), ("crc_out", crc_out)):
+        if a is not None and (not isinstance(a, np.ndarray) or a.dtype != np.uint32 or a.shape != shape
+                              or not a.flags["C_CONTIGUOUS"]):
+            raise ValueError(f"{name} must be a C-contiguous uint32 array {list(shape)}")
+    if crc_out is not None and not crc_out.flags["WRITEABLE"]:
+        raise ValueError("crc_out must be writable")
+    crc = crc_out if crc_out is not None else np.empty(shape, dtype=np.uint32)
+    if L == 0 and crc is not crc_in:  # the call touches nothing: every CRC continues over no bytes
+        crc[...] = 0 if crc_in is None else crc_in
+    return (None if crc_in is None else crc_in.ctypes.data), crc
+
+
 def _host_ptr(a, name, writable=False):
     """Base address of a host batch (numpy array or CPU tensor, pinned or not)."""
     torch = _lib.torch
@@ -206,6 +252,47 @@ def encode_batch_host(code, stripes):
     if len(sshape) != 3 or sshape[1] != n or sstr[2] != 1:
         raise ValueError(f"stripes must be [S, {n}, L] with unit byte stride")
     code._check(_lib.lib().hrs_encode_batch_host(code._handle(), sp, sstr[1], sstr[0], sshape[2], sshape[0]))
+
+
+def decode_batch_host_crc(code, stripes, erased, out, crc_in=None, crc_out=None):
+    """hrs_decode_batch_host_crc: decode_batch_host plus the CRC-32 of every
+    repaired cell, computed on the GPU in the same pass: returns a numpy uint32
+    array [S, E] (entry [s, t] for output t of stripe s; entries past a
+    stripe's losses keep their crc_in value, 0 without crc_in). crc_in (uint32
+    [S, E]) continues running CRCs; crc_out: the array to fill and return (it
+    may be crc_in itself) instead of a new one."""
+    n = code.stripeSize() + code.paritySize()
+    sp, sshape, sstr = _host_ptr(stripes, "stripes")
+    op, oshape, ostr = _host_ptr(out, "out", writable=True)
+    e = np.ascontiguousarray(np.asarray(erased, dtype=np.int32))
+    if len(sshape) != 3 or sshape[1] != n or sstr[2] != 1:
+        raise ValueError(f"stripes must be [S, {n}, L] with unit byte stride")
+    S, L = sshape[0], sshape[2]
+    if e.ndim != 2 or e.shape[0] != S:
+        raise ValueError("erased must be [S, E]")
+    if len(oshape) != 3 or tuple(oshape) != (S, e.shape[1], L) or ostr[2] != 1:
+        raise ValueError("out must be [S, E, L]")
+    cin, crc = _host_crcs((S, e.shape[1]), L, crc_in, crc_out)
+    code._check(_lib.lib().hrs_decode_batch_host_crc(
+        code._handle(), sp, sstr[1], sstr[0], e.ctypes.data, e.shape[1], op, ostr[1], ostr[0], L, S, cin,
+        crc.ctypes.data))
+    return crc
+
+
+def encode_batch_host_crc(code, stripes, crc_in=None, crc_out=None):
+    """hrs_encode_batch_host_crc: encode_batch_host plus the CRC-32 of every
+    cell, as Encoder.encodeStripe keeps them with computeBlockChecksum: returns
+    a numpy uint32 array [S, k + p], columns [source 0..k-1, parity 0..p-1]
+    (encode_stripes_crc's order). crc_in (same layout) continues running CRCs;
+    crc_out: the array to fill and return (it may be crc_in itself)."""
+    n = code.stripeSize() + code.paritySize()
+    sp, sshape, sstr = _host_ptr(stripes, "stripes", writable=True)
+    if len(sshape) != 3 or sshape[1] != n or sstr[2] != 1:
+        raise ValueError(f"stripes must be [S, {n}, L] with unit byte stride")
+    cin, crc = _host_crcs((sshape[0], n), sshape[2], crc_in, crc_out)
+    code._check(_lib.lib().hrs_encode_batch_host_crc(code._handle(), sp, sstr[1], sstr[0], sshape[2], sshape[0], cin,
+                                                     crc.ctypes.data))
+    return crc
 
 
 def _codec_array(codes):
