@@ -82,12 +82,23 @@ build/hrs_scrub.o: lambdafs_amd/csrc/hrs_scrub.hip $(HDRS)
 	@mkdir -p build
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
+# scrub / heal + CRC-32 in one pass. `make scrub_crc_resources` prints the
+# compiler's resource report of every fused instantiation (no scratch allowed).
+build/hrs_scrub_crc.o: lambdafs_amd/csrc/hrs_scrub_crc.hip $(HDRS)
+	@mkdir -p build
+	$(HIPCC) $(HIPFLAGS) -c $< -o $@
+
+scrub_crc_resources: lambdafs_amd/csrc/hrs_scrub_crc.hip $(HDRS)
+	@mkdir -p build
+	$(HIPCC) $(HIPFLAGS) -Rpass-analysis=kernel-resource-usage -c $< -o build/hrs_scrub_crc.report.o 2>&1 | \
+	    grep -E 'Function Name|VGPRs:|ScratchSize|Occupancy|LDS Size'
+
 build/hrs_probe.o: lambdafs_amd/csrc/hrs_probe.hip include/hrs_probe.h $(HDRS)
 	@mkdir -p build
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
 KOBJ     := build/hrs_kernels.o build/hrs_runtime.o build/hrs_batch.o build/hrs_crc.o build/hrs_fused.o build/hrs_decode_crc.o \
-            build/hrs_batch_crc.o build/hrs_gate.o build/hrs_scrub.o
+            build/hrs_batch_crc.o build/hrs_gate.o build/hrs_scrub.o build/hrs_scrub_crc.o
 
 $(LIB): $(API_OBJ) $(KOBJ) lambdafs_amd/csrc/libhrs.map
 	$(HIPCC) $(HIPFLAGS) -shared -Wl,--version-script=lambdafs_amd/csrc/libhrs.map -o $@ $(API_OBJ) $(KOBJ) \
@@ -214,4 +225,4 @@ tsan: tests/cpp/copy_pool_test.cpp lambdafs_amd/csrc/hrs_host.hpp
 clean:
 	rm -rf build $(LIB) $(ORACLE) $(JNI) $(HARNESS) $(TOOLS)
 
-.PHONY: all tsan clean asan
+.PHONY: all tsan clean asan scrub_crc_resources

@@ -561,6 +561,60 @@ hrs_status hrs_heal_batch_host(hrs_codec* codec, uint8_t* stripes, size_t row_st
  * the kernels run. report: 4 + n words. len == 0: nothing is touched. */
 hrs_status hrs_heal_host(const hrs_codec* codec, uint8_t* const* rows, size_t len, uint32_t* report);
 
+/* ---- scrub and heal + CRC-32: the block checksums in the same pass ----
+ * In the reference system a bad cell is first known by its block checksum
+ * (Encoder.java:408-450 stores one per block; Decoder.java:373-387 turns a
+ * ChecksumException into an erased location), and a checksum mismatch names
+ * up to parity_size bad cells where the syndromes stop at parity_size / 2;
+ * the syndromes in turn see a stale parity cell whose checksum was rewritten
+ * with it. These are the four scrub / heal calls above with the CRC-32 of
+ * every cell computed from the same read. The common rules of "batches +
+ * CRC-32" hold (chaining from crc_in, NULL crc_in = fresh, crc_out may be
+ * crc_in itself and any other overlap is HRS_EINVAL, a NULL crc_out with work
+ * to do is HRS_EINVAL, len == 0 or nstripes == 0 touches nothing, argument
+ * errors before the device, HRS_EDEVICE for a host-only handle), and:
+ *  - crc_out[s * n + l] belongs to hops location l of stripe s: HOPS ORDER,
+ *    parity first, the order of rows[] - NOT the data-first order of
+ *    hrs_encode_crc_dev and hrs_encode_batch_host_crc;
+ *  - scrub: the CRCs cover the cells as read; nothing is written to them;
+ *  - heal: the CRCs cover the cells as they are when the call returns, after
+ *    the write-back: the value to compare with the stored checksum to decide
+ *    whether the heal restored the block (an unresolved column is left as it
+ *    was and its cell's CRC says so);
+ *  - reports, the bytes healed, the bytes left untouched and every argument
+ *    rule are exactly the sibling call's.
+ * rs codes with 2 <= parity_size <= 4 and n <= 16, len a multiple of 2 KiB,
+ * 16-byte aligned rows and stride, kernel mode 0 or 3 take one fused kernel
+ * (hrs_last_kernel "scrub_crc_kernel<P>" / "heal_crc_kernel<P>"; the heal
+ * re-reads only the 2 KiB windows it patched); anything else runs the sibling
+ * call, then the CRC pass over the n rows, with identical results (and
+ * hrs_last_kernel as the sibling reports it). */
+
+/* hrs_scrub_dev + the CRCs. crc_in / crc_out: DEVICE uint32 [nstripes * n].
+ * Asynchronous on stream. */
+hrs_status hrs_scrub_crc_dev(hrs_codec* codec, const uint8_t* const* rows, size_t stride, size_t len,
+                             size_t nstripes, uint32_t* reports, size_t report_stride, const uint32_t* crc_in,
+                             uint32_t* crc_out, void* stream);
+
+/* hrs_heal_dev + the CRCs of the cells after the write-back. */
+hrs_status hrs_heal_crc_dev(hrs_codec* codec, uint8_t* const* rows, size_t stride, size_t len, size_t nstripes,
+                            uint32_t* reports, size_t report_stride, const uint32_t* crc_in, uint32_t* crc_out,
+                            void* stream);
+
+/* hrs_scrub_batch_host + the CRCs; crc_in / crc_out are HOST uint32
+ * [nstripes * n] (read before the first chunk, written once after the last).
+ * Runtime-pinned stripes of a fused shape cross the host link once.
+ * Synchronous. */
+hrs_status hrs_scrub_batch_host_crc(hrs_codec* codec, const uint8_t* stripes, size_t row_stride,
+                                    size_t stripe_stride, size_t len, size_t nstripes, uint32_t* reports,
+                                    size_t report_stride, const uint32_t* crc_in, uint32_t* crc_out);
+
+/* hrs_heal_batch_host + the CRCs of the cells after the write-back; staged
+ * cells go back to the caller exactly as for hrs_heal_batch_host. */
+hrs_status hrs_heal_batch_host_crc(hrs_codec* codec, uint8_t* stripes, size_t row_stride, size_t stripe_stride,
+                                   size_t len, size_t nstripes, uint32_t* reports, size_t report_stride,
+                                   const uint32_t* crc_in, uint32_t* crc_out);
+
 /* Kernel selection for tests and benchmarks: 0 = auto (default), 1 = force
  * the runtime-matrix bit-sliced kernel, 2 = force the byte-granular kernel,
  * 3 = auto, except that hrs_encode_crc_dev takes the fused kernel whenever the

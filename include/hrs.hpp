@@ -312,6 +312,39 @@ class HipReedSolomonCode : public HipCode {
     check(hrs_heal_batch_host(h_, stripes, rowStride, stripeStride, len, nstripes, reports, reportStride), h_);
   }
 
+  // scrubDev / healDev plus the CRC-32 of every cell from the same read
+  // (hrs_scrub_crc_dev / hrs_heal_crc_dev): crcOut[s * n + l] in HOPS order
+  // (parity first, the order of rows), continued from crcIn (nullptr: fresh);
+  // device arrays. The heal's CRCs cover the cells after the write-back.
+  void scrubCrcDev(const std::vector<const uint8_t*>& rows, size_t stride, size_t len, size_t nstripes,
+                   uint32_t* reports, size_t reportStride, const uint32_t* crcIn, uint32_t* crcOut,
+                   void* stream = nullptr) {
+    if (static_cast<int>(rows.size()) != stripeSize() + paritySize())
+      throw std::invalid_argument("scrubCrcDev: row count does not match the codec");
+    check(hrs_scrub_crc_dev(h_, rows.data(), stride, len, nstripes, reports, reportStride, crcIn, crcOut, stream), h_);
+  }
+
+  void healCrcDev(const std::vector<uint8_t*>& rows, size_t stride, size_t len, size_t nstripes, uint32_t* reports,
+                  size_t reportStride, const uint32_t* crcIn, uint32_t* crcOut, void* stream = nullptr) {
+    if (static_cast<int>(rows.size()) != stripeSize() + paritySize())
+      throw std::invalid_argument("healCrcDev: row count does not match the codec");
+    check(hrs_heal_crc_dev(h_, rows.data(), stride, len, nstripes, reports, reportStride, crcIn, crcOut, stream), h_);
+  }
+
+  // The same over a host batch (hrs_scrub_batch_host_crc /
+  // hrs_heal_batch_host_crc); reports, crcIn and crcOut are host arrays.
+  void scrubBatchHostCrc(const uint8_t* stripes, size_t rowStride, size_t stripeStride, size_t len, size_t nstripes,
+                         uint32_t* reports, size_t reportStride, const uint32_t* crcIn, uint32_t* crcOut) {
+    check(hrs_scrub_batch_host_crc(h_, stripes, rowStride, stripeStride, len, nstripes, reports, reportStride, crcIn,
+                                   crcOut), h_);
+  }
+
+  void healBatchHostCrc(uint8_t* stripes, size_t rowStride, size_t stripeStride, size_t len, size_t nstripes,
+                        uint32_t* reports, size_t reportStride, const uint32_t* crcIn, uint32_t* crcOut) {
+    check(hrs_heal_batch_host_crc(h_, stripes, rowStride, stripeStride, len, nstripes, reports, reportStride, crcIn,
+                                  crcOut), h_);
+  }
+
   // One stripe of n host rows healed on the CPU (hrs_heal_host; host-only
   // handles included); report holds HRS_SCRUB_HEAD + n words.
   void healHost(const std::vector<uint8_t*>& rows, size_t len, uint32_t* report) {

@@ -944,11 +944,32 @@ hrs_status encode_batch_host_impl(hrs_codec* c, uint8_t* stripes, size_t row_str
 // read. Pinned stripes are patched in place across the link; a staged chunk's
 // reports are fetched when its kernels have finished and the cells with a
 // nonzero count in word 4 + l go back to the caller (host_batch's dirty hook).
+// crc_out != NULL (hrs_scrub_batch_host_crc, hrs_heal_batch_host_crc; HOST
+// arrays of nstripes * n words, hops order): run_scrub_crc instead of
+// run_scrub, the CRCs through the handle's device buffer as in
+// encode_batch_host_impl. A pinned cell crosses the link once when the shape
+// takes the one-pass kernel (the heal's dirty windows twice).
 hrs_status scrub_batch_host_impl(hrs_codec* c, const uint8_t* stripes, size_t row_stride, size_t stripe_stride,
-                                 size_t len, size_t nstripes, uint32_t* reports, size_t report_stride, bool heal) {
+                                 size_t len, size_t nstripes, uint32_t* reports, size_t report_stride, bool heal,
+                                 const uint32_t* crc_in = nullptr, uint32_t* crc_out = nullptr) {
   DeviceGuard g(c->device);
   if (!g.ok) return fail(c, HRS_EDEVICE, "cannot select HIP device %d", c->device);
   const int n = c->n;
+  const size_t ncrc = nstripes * static_cast<size_t>(n);
+  const uint32_t* dcrc_in = nullptr;
+  if (crc_out) {
+    hrs_status cs = hbatch_crc_buffer(c, ncrc, crc_in);
+    if (cs != HRS_OK) return cs;
+    if (crc_in) dcrc_in = c->hbatch_crc;
+  }
+  uint32_t* const dcrc = crc_out ? c->hbatch_crc : nullptr;
+  // the scrub or heal of stripes [s0, s0 + ns) on hs, with their CRCs when asked
+  auto scrub = [&](const uint8_t* const* r, size_t stride, size_t s0, size_t ns, uint32_t* rep,
+                   hipStream_t hs) -> hrs_status {
+    if (!dcrc) return run_scrub(c, r, stride, len, ns, rep, static_cast<size_t>(hrs::kScrubHead + n), hs, heal);
+    return run_scrub_crc(c, r, stride, len, ns, rep, static_cast<size_t>(hrs::kScrubHead + n),
+                         dcrc_in ? dcrc_in + s0 * n : nullptr, dcrc + s0 * n, hs, heal);
+  };
   const size_t nwords = static_cast<size_t>(hrs::kScrubHead + n);
   const size_t bytes = nstripes * nwords * sizeof(uint32_t);
   if (c->scrub_reports_bytes < bytes) {  // every earlier batch has completed: the calls are synchronous
@@ -970,7 +991,7 @@ hrs_status scrub_batch_host_impl(hrs_codec* c, const uint8_t* stripes, size_t ro
     for (int l = 0; l < n; ++l) rows[l] = zs + static_cast<size_t>(l) * row_stride;
     {
       hrs::GridCap cap(zero_copy_blocks());
-      st = run_scrub(c, rows.data(), stripe_stride, len, nstripes, drep, nwords, hs, heal);
+      st = scrub(rows.data(), stripe_stride, 0, nstripes, drep, hs);
     }
     if (st == HRS_OK) {
       const hipError_t e = hipStreamSynchronize(hs);
@@ -983,7 +1004,7 @@ hrs_status scrub_batch_host_impl(hrs_codec* c, const uint8_t* stripes, size_t ro
     auto compute = [&](hipStream_t hs, size_t s0, size_t ns, uint8_t* dimg, size_t img_stripe, size_t dpitch, uint8_t*,
                        size_t) -> hrs_status {
       for (int l = 0; l < n; ++l) rows[l] = dimg + static_cast<size_t>(l) * dpitch;
-      return run_scrub(c, rows.data(), img_stripe, len, ns, drep + s0 * nwords, nwords, hs, heal);
+      return scrub(rows.data(), img_stripe, s0, ns, drep + s0 * nwords, hs);
     };
     std::vector<uint32_t> chunk_rep;
     auto dirty = [&](size_t s0, size_t ns, std::vector<DirtyCell>& cells) -> hrs_status {
@@ -1008,12 +1029,14 @@ hrs_status scrub_batch_host_impl(hrs_codec* c, const uint8_t* stripes, size_t ro
   if (e != hipSuccess) return hip_fail(c, e, "hipMemcpy reports");
   for (size_t s = 0; s < nstripes; ++s)
     std::memcpy(reports + s * report_stride, host.data() + s * nwords, nwords * sizeof(uint32_t));
-  return HRS_OK;
+  return crc_out ? hbatch_crc_fetch(c, ncrc, crc_out) : HRS_OK;
 }
 
 // hrs_scrub_batch_host and hrs_heal_batch_host: one set of argument rules.
 hrs_status scrub_batch_host_entry(hrs_codec* c, const uint8_t* stripes, size_t row_stride, size_t stripe_stride,
-                                  size_t len, size_t nstripes, uint32_t* reports, size_t report_stride, bool heal) {
+                                  size_t len, size_t nstripes, uint32_t* reports, size_t report_stride, bool heal,
+                                  bool with_crc = false, const uint32_t* crc_in = nullptr,
+                                  uint32_t* crc_out = nullptr) {
   if (!c) return HRS_EINVAL;
   hrs_status st = scrub_code_ok(c, report_stride, true);
   if (st != HRS_OK) return st;
@@ -1031,7 +1054,13 @@ hrs_status scrub_batch_host_entry(hrs_codec* c, const uint8_t* stripes, size_t r
   if (row_stride < len || !stripes_apart)
     return fail(c, HRS_EINVAL, "cells overlap: row_stride %zu, stripe_stride %zu, len %zu, %d rows, %zu stripes",
                 row_stride, stripe_stride, len, c->n, nstripes);
-  st = scrub_batch_host_impl(c, stripes, row_stride, stripe_stride, len, nstripes, reports, report_stride, heal);
+  if (with_crc) {
+    if (!crc_out) return fail(c, HRS_EINVAL, "crc_out is NULL");
+    if (!crc_arrays_apart(crc_in, crc_out, nstripes * static_cast<size_t>(c->n)))
+      return fail(c, HRS_EINVAL, "crc_in and crc_out overlap (crc_out may only be crc_in itself)");
+  }
+  st = scrub_batch_host_impl(c, stripes, row_stride, stripe_stride, len, nstripes, reports, report_stride, heal,
+                             crc_in, crc_out);
   if (st == HRS_OK) {
     DeviceGuard g(c->device);
     c->last_host_path =
@@ -1052,6 +1081,20 @@ hrs_status hrs_scrub_batch_host(hrs_codec* c, const uint8_t* stripes, size_t row
 hrs_status hrs_heal_batch_host(hrs_codec* c, uint8_t* stripes, size_t row_stride, size_t stripe_stride, size_t len,
                                size_t nstripes, uint32_t* reports, size_t report_stride) {
   return scrub_batch_host_entry(c, stripes, row_stride, stripe_stride, len, nstripes, reports, report_stride, true);
+}
+
+hrs_status hrs_scrub_batch_host_crc(hrs_codec* c, const uint8_t* stripes, size_t row_stride, size_t stripe_stride,
+                                    size_t len, size_t nstripes, uint32_t* reports, size_t report_stride,
+                                    const uint32_t* crc_in, uint32_t* crc_out) {
+  return scrub_batch_host_entry(c, stripes, row_stride, stripe_stride, len, nstripes, reports, report_stride, false,
+                                true, crc_in, crc_out);
+}
+
+hrs_status hrs_heal_batch_host_crc(hrs_codec* c, uint8_t* stripes, size_t row_stride, size_t stripe_stride, size_t len,
+                                   size_t nstripes, uint32_t* reports, size_t report_stride, const uint32_t* crc_in,
+                                   uint32_t* crc_out) {
+  return scrub_batch_host_entry(c, stripes, row_stride, stripe_stride, len, nstripes, reports, report_stride, true,
+                                true, crc_in, crc_out);
 }
 
 hrs_status hrs_decode_batch_dev(hrs_codec* c, const uint8_t* stripes, size_t row_stride, size_t stripe_stride,

@@ -272,6 +272,25 @@ hrs_status run_scrub(hrs_codec* c, const uint8_t* const* rows, size_t stride, si
                      uint32_t* reports, size_t report_stride, hipStream_t s, bool heal);
 // The rows of a heal call: none NULL, no two equal (HRS_EINVAL).
 hrs_status heal_rows_ok(hrs_codec* c, const uint8_t* const* rows);
+// run_scrub plus the CRC-32 of every cell (hrs_scrub_crc_dev's semantics:
+// crc_out[s * n + l], hops order, DEVICE arrays; the heal's cover the cells
+// after the write-back). One pass (hrs_scrub_crc.hip) when
+// scrub_crc_one_pass holds, else run_scrub, then the CRC pass over the n
+// rows. Takes and releases the handle's raw-CRC scratch on stream s.
+hrs_status run_scrub_crc(hrs_codec* c, const uint8_t* const* rows, size_t stride, size_t len, size_t nstripes,
+                         uint32_t* reports, size_t report_stride, const uint32_t* crc_in, uint32_t* crc_out,
+                         hipStream_t s, bool heal);
+// 2 <= p <= 4, n <= 16, whole 2 KiB windows, 16-byte aligned rows and stride,
+// kernel mode 0 or 3.
+bool scrub_crc_one_pass(const hrs_codec* c, const uint8_t* const* rows, size_t stride, size_t len);
+
+// ---- shared by the CRC entry points
+// crc_out may be crc_in itself; any other overlap of the two n-word arrays is refused (hrs_batch_api.cpp).
+bool crc_arrays_apart(const uint32_t* crc_in, const uint32_t* crc_out, size_t n);
+// The fold alone (hrs_dispatch.cpp): raw window CRCs of nsr (stripe, row)
+// pairs, windows of `win` bytes, into crc_out, continuing crc_in.
+hrs_status crc_fold_windows(hrs_codec* c, size_t len, uint64_t nsr, const uint32_t* crc_in, uint32_t* crc_out,
+                            hipStream_t s, uint32_t* raw, uint64_t win);
 
 }  // namespace hrs::api
 #pragma GCC visibility pop

@@ -139,4 +139,35 @@ struct BatchCrcFoldArgs {
 };
 hipError_t launch_batch_crc_fold(const BatchCrcFoldArgs& b, int cus, hipStream_t s);
 
+// Fused scrub / heal + CRC-32 (hrs_scrub_crc.hip): scrub_kernel's walk over
+// whole 2 KiB windows (ntasks = nwin * stripes, 16-byte aligned rows and
+// stride) with the raw CRC of every location's window in
+// raw[(stripe * n + l) * nwin + window], hops order (crc_fold_kernel finishes
+// them with 2 KiB windows). Shapes: 2 <= p <= kScrubCrcMaxP and
+// n <= kScrubCrcMaxRows; anything else is hipErrorInvalidValue (the host
+// checks first).
+// heal: the kernel also writes the resolved columns back and lists every task
+// in which it stored a byte in `dirty` (dirty[0] = how many, zeroed by the
+// caller; dirty[1 + i] = task; room for ntasks). launch_scrub_crc_redo, after
+// it on the same stream, rewrites the raw words of the listed windows from
+// the bytes as they are then.
+constexpr int kScrubCrcMaxRows = 16;
+constexpr int kScrubCrcMaxP = 4;
+struct ScrubCrcArgs {
+  const uint8_t* rows[kScrubCrcMaxRows];  // location l of stripe s at rows[l] + s * stride
+  uint64_t stride;
+  uint64_t nwin;     // 2 KiB windows per row (len / 2 KiB, len a multiple)
+  uint64_t ntasks;   // nstripes * nwin
+  uint32_t* reports;  // initialised (launch_scrub_init); stripe s at reports + s * report_stride
+  uint64_t report_stride;
+  uint32_t* raw;
+  const uint32_t* tables;  // kCrcLdsWordsA words (device)
+  uint64_t* dirty;         // heal only
+  int n, p;
+  int order;  // window -> wave order (task_order), set at launch
+  int pad_;
+};
+hipError_t launch_scrub_crc(const ScrubCrcArgs& a, bool heal, int cus, hipStream_t s);
+hipError_t launch_scrub_crc_redo(const ScrubCrcArgs& a, int cus, hipStream_t s);
+
 }  // namespace hrs

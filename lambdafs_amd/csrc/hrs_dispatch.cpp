@@ -368,6 +368,11 @@ hrs_status crc_fold(hrs_codec* c, size_t len, uint64_t nsr, const uint32_t* crc_
   return fold_tables_used(c, ft, s);  // the tables may be freed once this fold has run
 }
 
+hrs_status crc_fold_windows(hrs_codec* c, size_t len, uint64_t nsr, const uint32_t* crc_in, uint32_t* crc_out,
+                            hipStream_t s, uint32_t* raw, uint64_t win) {
+  return crc_fold(c, len, nsr, crc_in, crc_out, s, raw, win);
+}
+
 // Sub-windows (2 KiB) per fused window: 16 (32 KiB) when the job has
 // kFusedWavesPerCU waves per CU at that size, else the largest smaller power
 // of two that does (down to 1: a job with fewer 2 KiB sub-windows than that

@@ -1,14 +1,19 @@
 // Stripe scrubbing and healing behind the C ABI: the scalar
 // computeErrorLocations on the host (hrs_compute_error_locations, host-only
-// handles included), the device-resident batches (hrs_scrub_dev, hrs_heal_dev)
-// and one stripe healed on the CPU (hrs_heal_host). The host-memory batches are
+// handles included), the device-resident batches (hrs_scrub_dev, hrs_heal_dev,
+// and hrs_scrub_crc_dev, hrs_heal_crc_dev with the cells' CRC-32s from the same
+// pass) and one stripe healed on the CPU (hrs_heal_host). The host-memory batches are
 // in hrs_batch_api.cpp beside the pipeline they share. The per-column algorithm
 // is hrs_locator.hpp, the same code the kernels of hrs_scrub.hip run.
 #include <hip/hip_runtime.h>
 
+#include <string>
+#include <vector>
+
 #include "../../include/hrs.h"
 #include "gf256.hpp"
 #include "hrs_codec.hpp"
+#include "hrs_crc.hpp"
 #include "hrs_internal.hpp"
 #include "hrs_locator.hpp"
 
@@ -113,6 +118,100 @@ hrs_status heal_rows_ok(hrs_codec* c, const uint8_t* const* rows) {
   return HRS_OK;
 }
 
+// The shapes of the one-pass kernel (hrs_scrub_crc.hip). Device-resident jobs
+// take it too: measured 13 % faster than scrub + hrs_crc32_dev.
+bool scrub_crc_one_pass(const hrs_codec* c, const uint8_t* const* rows, size_t stride, size_t len) {
+  if (c->p < 2 || c->p > hrs::kScrubCrcMaxP || c->n > hrs::kScrubCrcMaxRows) return false;
+  if (!(c->kernel_mode == 0 || c->kernel_mode == 3)) return false;
+  if (len == 0 || len % hrs::kWindowBytes != 0 || stride % 16 != 0) return false;
+  for (int l = 0; l < c->n; ++l)
+    if (!aligned16(rows[l])) return false;
+  return true;
+}
+
+hrs_status run_scrub_crc(hrs_codec* c, const uint8_t* const* rows, size_t stride, size_t len, size_t nstripes,
+                         uint32_t* reports, size_t report_stride, const uint32_t* crc_in, uint32_t* crc_out,
+                         hipStream_t s, bool heal) {
+  const int n = c->n;
+  if (!scrub_crc_one_pass(c, rows, stride, len)) {
+    // two passes: the scrub or heal as it is, then the CRC of the n rows (the
+    // stream orders the heal's stores before the CRC pass reads them)
+    hrs_status st = run_scrub(c, rows, stride, len, nstripes, reports, report_stride, s, heal);
+    if (st != HRS_OK) return st;
+    const std::string kernel = c->last_kernel;
+    st = crc_scratch(c, crc_raw_bytes_for(len, nstripes, n), s);
+    if (st != HRS_OK) return st;
+    const std::vector<size_t> strides(n, stride);
+    st = crc_scratch_release(c, s, run_crc(c, rows, strides.data(), n, len, nstripes, crc_in, crc_out, s, c->crc_raw));
+    c->last_kernel = kernel;
+    return st;
+  }
+  hipError_t e = hrs::launch_scrub_init(reports, report_stride, n, nstripes, s);
+  if (e != hipSuccess) return hip_fail(c, e, "scrub init launch");
+  hrs_status st = crc_window_tables(c);
+  if (st != HRS_OK) return st;
+  hrs::ScrubCrcArgs a{};
+  for (int l = 0; l < n; ++l) a.rows[l] = rows[l];
+  a.stride = stride;
+  a.nwin = len / hrs::kWindowBytes;
+  a.ntasks = a.nwin * nstripes;
+  a.reports = reports;
+  a.report_stride = report_stride;
+  a.n = n;
+  a.p = c->p;
+  a.tables = c->crc_tables_a;
+  // scratch: the raw window CRCs, then (heal) the dirty-task count and list
+  const size_t raw_bytes = (a.ntasks * static_cast<size_t>(n) * 4 + 7) & ~static_cast<size_t>(7);
+  const size_t list_bytes = heal ? (1 + a.ntasks) * sizeof(uint64_t) : 0;
+  st = crc_scratch(c, raw_bytes + list_bytes, s);
+  if (st != HRS_OK) return st;
+  a.raw = c->crc_raw;
+  a.dirty = heal ? reinterpret_cast<uint64_t*>(reinterpret_cast<uint8_t*>(c->crc_raw) + raw_bytes) : nullptr;
+  const int cus = hrs::device_cu_count();
+  auto launches = [&]() -> hrs_status {
+    if (heal && (e = hipMemsetAsync(a.dirty, 0, sizeof(uint64_t), s)) != hipSuccess)
+      return hip_fail(c, e, "hipMemsetAsync");
+    if ((e = hrs::launch_scrub_crc(a, heal, cus, s)) != hipSuccess)
+      return hip_fail(c, e, heal ? "heal+crc launch" : "scrub+crc launch");
+    c->last_kernel = hrs::last_kernel();
+    if (heal && (e = hrs::launch_scrub_crc_redo(a, cus, s)) != hipSuccess) return hip_fail(c, e, "crc redo launch");
+    return crc_fold_windows(c, len, nstripes * static_cast<uint64_t>(n), crc_in, crc_out, s, c->crc_raw,
+                            hrs::kWindowBytes);
+  };
+  return crc_scratch_release(c, s, launches());
+}
+
+namespace {
+
+// hrs_scrub_crc_dev and hrs_heal_crc_dev: the sibling call's argument rules, then the CRC arrays'.
+hrs_status scrub_crc_dev_entry(hrs_codec* c, const uint8_t* const* rows, size_t stride, size_t len, size_t nstripes,
+                               uint32_t* reports, size_t report_stride, const uint32_t* crc_in, uint32_t* crc_out,
+                               void* stream, bool heal) {
+  if (!c) return HRS_EINVAL;
+  hrs_status st = scrub_code_ok(c, report_stride, true);
+  if (st != HRS_OK) return st;
+  if (!rows || !reports) return fail(c, HRS_EINVAL, "rows or reports is NULL");
+  if (heal) {
+    st = heal_rows_ok(c, rows);
+    if (st != HRS_OK) return st;
+  } else {
+    for (int l = 0; l < c->n; ++l)
+      if (!rows[l]) return fail(c, HRS_EINVAL, "row %d is NULL", l);
+  }
+  if (nstripes > 0x7fffffffu) return fail(c, HRS_EINVAL, "too many stripes");
+  if (len > 0xffffffffu) return fail(c, HRS_EINVAL, "rows of %zu bytes: column indices are 32-bit", len);
+  if (len == 0 || nstripes == 0) return HRS_OK;
+  if (!crc_out) return fail(c, HRS_EINVAL, "crc_out is NULL");
+  if (!crc_arrays_apart(crc_in, crc_out, nstripes * static_cast<size_t>(c->n)))
+    return fail(c, HRS_EINVAL, "crc_in and crc_out overlap (crc_out may only be crc_in itself)");
+  DeviceGuard g(c->device);
+  if (!g.ok) return fail(c, HRS_EDEVICE, "cannot select HIP device %d", c->device);
+  return run_scrub_crc(c, rows, stride, len, nstripes, reports, report_stride, crc_in, crc_out,
+                       static_cast<hipStream_t>(stream), heal);
+}
+
+}  // namespace
+
 }  // namespace hrs::api
 
 using namespace hrs::api;
@@ -189,6 +288,18 @@ hrs_status hrs_heal_dev(hrs_codec* c, uint8_t* const* rows, size_t stride, size_
   DeviceGuard g(c->device);
   if (!g.ok) return fail(c, HRS_EDEVICE, "cannot select HIP device %d", c->device);
   return run_scrub(c, rows, stride, len, nstripes, reports, report_stride, static_cast<hipStream_t>(stream), true);
+}
+
+hrs_status hrs_scrub_crc_dev(hrs_codec* c, const uint8_t* const* rows, size_t stride, size_t len, size_t nstripes,
+                             uint32_t* reports, size_t report_stride, const uint32_t* crc_in, uint32_t* crc_out,
+                             void* stream) {
+  return scrub_crc_dev_entry(c, rows, stride, len, nstripes, reports, report_stride, crc_in, crc_out, stream, false);
+}
+
+hrs_status hrs_heal_crc_dev(hrs_codec* c, uint8_t* const* rows, size_t stride, size_t len, size_t nstripes,
+                            uint32_t* reports, size_t report_stride, const uint32_t* crc_in, uint32_t* crc_out,
+                            void* stream) {
+  return scrub_crc_dev_entry(c, rows, stride, len, nstripes, reports, report_stride, crc_in, crc_out, stream, true);
 }
 
 hrs_status hrs_heal_host(const hrs_codec* cc, uint8_t* const* rows, size_t len, uint32_t* report) {

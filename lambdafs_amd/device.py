@@ -479,6 +479,137 @@ def scrub_to_erased(reports, p):
     return erased
 
 
+def _scrub_crc(code, rows, stride, L, S, ref, crc_in, heal):
+    torch = _lib.torch
+    n = code.stripeSize() + code.paritySize()
+    reports = torch.empty((S, SCRUB_HEAD + n), dtype=torch.int32, device=ref.device)
+    crc = torch.empty((S, n), dtype=torch.int32, device=ref.device)
+    cin = None
+    if crc_in is not None:
+        if crc_in.shape != crc.shape or crc_in.dtype != torch.int32 or not crc_in.is_contiguous() \
+                or crc_in.device != ref.device:
+            raise ValueError(f"crc_in must be a contiguous int32 device tensor [S, {n}]")
+        cin = crc_in.data_ptr()
+    if L == 0 or S == 0:  # the call touches nothing: every CRC continues over no bytes
+        crc.zero_() if crc_in is None else crc.copy_(crc_in)
+    call = _lib.lib().hrs_heal_crc_dev if heal else _lib.lib().hrs_scrub_crc_dev
+    code._check(call(code._handle(), rows, stride, L, S, reports.data_ptr(), SCRUB_HEAD + n, cin, crc.data_ptr(),
+                     _stream(ref)))
+    return reports, crc
+
+
+def scrub_stripes_crc(code, stripes, crc_in=None):
+    """scrub_stripes plus the CRC-32 (java.util.zip.CRC32) of every cell from
+    the same read (hrs_scrub_crc_dev): returns (reports, crcs), crcs an int32
+    tensor [S, n] of the uint32 CRC bits in HOPS order (column l = location l,
+    parity first; not encode_stripes_crc's data-first order), as crc32_rows
+    returns it over the n rows. crc_in ([S, n] int32) continues running CRCs."""
+    n = code.stripeSize() + code.paritySize()
+    if stripes.dim() != 3 or stripes.shape[1] != n:
+        raise ValueError(f"stripes must be [S, {n}, L]")
+    rows, stride, L, S = _stripe_rows(stripes, range(n))
+    return _scrub_crc(code, rows, stride, L, S, stripes, crc_in, False)
+
+
+def scrub_rows_crc(code, row_views, crc_in=None):
+    """scrub_stripes_crc with explicit [S, L] row views, one per location in hops order."""
+    n = code.stripeSize() + code.paritySize()
+    if len(row_views) != n or any(v is None for v in row_views):
+        raise ValueError(f"need {n} row views")
+    rows, stride, L, S = _rows(row_views)
+    return _scrub_crc(code, rows, stride, L, S, row_views[0], crc_in, False)
+
+
+def heal_stripes_crc(code, stripes, crc_in=None):
+    """heal_stripes plus the CRC-32 of every cell AS IT IS AFTER the write-back
+    (hrs_heal_crc_dev): (reports, crcs) as for scrub_stripes_crc. A cell whose
+    CRC equals its stored checksum was restored."""
+    n = code.stripeSize() + code.paritySize()
+    if stripes.dim() != 3 or stripes.shape[1] != n:
+        raise ValueError(f"stripes must be [S, {n}, L]")
+    rows, stride, L, S = _stripe_rows(stripes, range(n))
+    return _scrub_crc(code, rows, stride, L, S, stripes, crc_in, True)
+
+
+def heal_rows_crc(code, row_views, crc_in=None):
+    """heal_stripes_crc with explicit [S, L] row views, one per location in hops order."""
+    n = code.stripeSize() + code.paritySize()
+    if len(row_views) != n or any(v is None for v in row_views):
+        raise ValueError(f"need {n} row views")
+    rows, stride, L, S = _rows(row_views)
+    return _scrub_crc(code, rows, stride, L, S, row_views[0], crc_in, True)
+
+
+def _scrub_batch_host_crc(code, stripes, crc_in, crc_out, heal):
+    n = code.stripeSize() + code.paritySize()
+    sp, sshape, sstr = _host_ptr(stripes, "stripes", writable=heal)
+    if len(sshape) != 3 or sshape[1] != n or sstr[2] != 1:
+        raise ValueError(f"stripes must be [S, {n}, L] with unit byte stride")
+    S, L = sshape[0], sshape[2]
+    cin, crc = _host_crcs((S, n), L, crc_in, crc_out)
+    reports = np.zeros((S, SCRUB_HEAD + n), dtype=np.uint32)
+    call = _lib.lib().hrs_heal_batch_host_crc if heal else _lib.lib().hrs_scrub_batch_host_crc
+    code._check(call(code._handle(), sp, sstr[1], sstr[0], L, S, reports.ctypes.data, SCRUB_HEAD + n, cin,
+                     crc.ctypes.data))
+    return reports, crc
+
+
+def scrub_batch_host_crc(code, stripes, crc_in=None, crc_out=None):
+    """hrs_scrub_batch_host_crc: scrub_batch_host plus the CRC-32 of every cell
+    from the same read: (reports, crcs), crcs a numpy uint32 array [S, n] in
+    HOPS order. crc_in (same layout) continues running CRCs; crc_out: the array
+    to fill and return (it may be crc_in itself)."""
+    return _scrub_batch_host_crc(code, stripes, crc_in, crc_out, False)
+
+
+def heal_batch_host_crc(code, stripes, crc_in=None, crc_out=None):
+    """hrs_heal_batch_host_crc: heal_batch_host plus the CRC-32 of every cell as
+    it is after the write-back; arguments and result as scrub_batch_host_crc."""
+    return _scrub_batch_host_crc(code, stripes, crc_in, crc_out, True)
+
+
+def checksums_to_erased(crcs, stored, p, reports=None):
+    """The int32 [S, p] erasure array decode_batch / decode_batch_crc take, from
+    the cell CRCs of a scrub ([S, n], hops order) and the stored checksums:
+    per stripe the locations whose CRC differs from `stored`, joined, when
+    `reports` ([S, 4 + n]) is given, by the locations with a nonzero count in
+    word 4 + l (a stale parity cell whose checksum was rewritten with it shows
+    only there); ascending, -1 padded. A checksum names up to p bad cells where
+    the syndromes stop at p / 2, so unresolved columns are no error here as
+    long as some checksum of the stripe differs. ValueError for a stripe with
+    more than p such locations, and for one with unresolved columns while no
+    checksum differs (the data and the checksums disagree in a way neither
+    names). scrub_to_erased is the rule for reports alone."""
+    torch = _lib.torch
+
+    def host(a):
+        if a is not None and torch is not None and isinstance(a, torch.Tensor):
+            a = a.cpu().numpy()
+        return None if a is None else np.asarray(a)
+
+    c, st, r = host(crcs), host(stored), host(reports)
+    if c.ndim != 2 or st.shape != c.shape:
+        raise ValueError("crcs and stored must both be [S, n]")
+    S, n = c.shape
+    differ = (c.astype(np.int64) & 0xFFFFFFFF) != (st.astype(np.int64) & 0xFFFFFFFF)
+    if r is not None:
+        if r.ndim != 2 or r.shape != (S, SCRUB_HEAD + n):
+            raise ValueError("reports must be [S, 4 + n]")
+        r = r.astype(np.int64) & 0xFFFFFFFF
+    erased = np.full((S, int(p)), -1, dtype=np.int32)
+    for s in range(S):
+        bad = differ[s].copy()
+        if r is not None:
+            if r[s, SCRUB_UNRESOLVED] and not differ[s].any():
+                raise ValueError(f"stripe {s}: {int(r[s, SCRUB_UNRESOLVED])} unresolved columns and no checksum differs")
+            bad |= r[s, SCRUB_HEAD:] != 0
+        locs = np.flatnonzero(bad)
+        if len(locs) > p:
+            raise ValueError(f"stripe {s}: {len(locs)} bad locations, the code repairs {int(p)}")
+        erased[s, : len(locs)] = locs
+    return erased
+
+
 PROBE_COPY, PROBE_READ, PROBE_WRITE = 0, 1, 2
 WAVE_TASKS, GRID_STRIDE, BLOCK_RANGE = 0, 1, 2  # hrs_probe_stream schedules
 
