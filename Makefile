@@ -11,16 +11,16 @@ PROBE    := lambdafs_amd/libhrs_probe.so
 ORACLE   := oracle/liboracle.so
 HDRS     := Makefile include/hrs.h lambdafs_amd/csrc/hrs_device.hpp lambdafs_amd/csrc/hrs_launch.hpp lambdafs_amd/csrc/gf256.hpp lambdafs_amd/csrc/hrs_internal.hpp \
             lambdafs_amd/csrc/crc32.hpp lambdafs_amd/csrc/hrs_crc.hpp lambdafs_amd/csrc/xor_sched.hpp lambdafs_amd/csrc/hrs_codec.hpp \
-            lambdafs_amd/csrc/hrs_host.hpp lambdafs_amd/csrc/hrs_locator.hpp
+            lambdafs_amd/csrc/hrs_host.hpp lambdafs_amd/csrc/hrs_locator.hpp lambdafs_amd/csrc/hrs_heal_erased.hpp
 
 # Host translation units of the C ABI (no kernels): lifecycle + queries,
 # matrices, device dispatch + CRC, host-buffer path, batches, scrubbing.
-API_SRC  := hrs_api hrs_matrix hrs_dispatch hrs_hostpath hrs_batch_api hrs_scrub_api
+API_SRC  := hrs_api hrs_matrix hrs_dispatch hrs_hostpath hrs_batch_api hrs_scrub_api hrs_heal_erased_api
 API_OBJ  := $(patsubst %,build/%.o,$(API_SRC))
 
 JNI      := lambdafs_amd/libhrs_jni.so
 HARNESS  := tests/cpp/codec_harness tests/cpp/crc_model tests/cpp/jni_harness tests/cpp/host_logic tests/cpp/crc_tables \
-            tests/cpp/copy_pool_test tests/cpp/scrub_logic tests/cpp/heal_logic
+            tests/cpp/copy_pool_test tests/cpp/scrub_logic tests/cpp/heal_logic tests/cpp/heal_erased_logic
 
 TOOLS    := tools/host_call_rate tools/host_pipeline_sweep tools/host_copy_probe
 
@@ -93,12 +93,23 @@ scrub_crc_resources: lambdafs_amd/csrc/hrs_scrub_crc.hip $(HDRS)
 	$(HIPCC) $(HIPFLAGS) -Rpass-analysis=kernel-resource-usage -c $< -o build/hrs_scrub_crc.report.o 2>&1 | \
 	    grep -E 'Function Name|VGPRs:|ScratchSize|Occupancy|LDS Size'
 
+# Heal with known erasures. `make heal_erased_resources` prints the compiler's
+# resource report of every instantiation (no scratch allowed).
+build/hrs_heal_erased.o: lambdafs_amd/csrc/hrs_heal_erased.hip $(HDRS)
+	@mkdir -p build
+	$(HIPCC) $(HIPFLAGS) -c $< -o $@
+
+heal_erased_resources: lambdafs_amd/csrc/hrs_heal_erased.hip $(HDRS)
+	@mkdir -p build
+	$(HIPCC) $(HIPFLAGS) -Rpass-analysis=kernel-resource-usage -c $< -o build/hrs_heal_erased.report.o 2>&1 | \
+	    grep -E 'Function Name|VGPRs:|ScratchSize|Occupancy|LDS Size'
+
 build/hrs_probe.o: lambdafs_amd/csrc/hrs_probe.hip include/hrs_probe.h $(HDRS)
 	@mkdir -p build
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
 KOBJ     := build/hrs_kernels.o build/hrs_runtime.o build/hrs_batch.o build/hrs_crc.o build/hrs_fused.o build/hrs_decode_crc.o \
-            build/hrs_batch_crc.o build/hrs_gate.o build/hrs_scrub.o build/hrs_scrub_crc.o
+            build/hrs_batch_crc.o build/hrs_gate.o build/hrs_scrub.o build/hrs_scrub_crc.o build/hrs_heal_erased.o
 
 $(LIB): $(API_OBJ) $(KOBJ) lambdafs_amd/csrc/libhrs.map
 	$(HIPCC) $(HIPFLAGS) -shared -Wl,--version-script=lambdafs_amd/csrc/libhrs.map -o $@ $(API_OBJ) $(KOBJ) \
@@ -143,6 +154,11 @@ tests/cpp/heal_logic: tests/cpp/heal_logic.cpp include/hrs.h $(LIB) $(ORACLE)
 	g++ -O2 -std=c++17 -Wall -Iinclude -Ioracle -o $@ $< -Llambdafs_amd -lhrs -Loracle -loracle \
 	    -Wl,-rpath,'$$ORIGIN/../../lambdafs_amd' -Wl,-rpath,'$$ORIGIN/../../oracle'
 
+# Heal with known erasures on the CPU (hrs_heal_erased_host): uniqueness, capacity, e = 0 vs hrs_heal_host.
+tests/cpp/heal_erased_logic: tests/cpp/heal_erased_logic.cpp include/hrs.h $(LIB) $(ORACLE)
+	g++ -O2 -std=c++17 -Wall -Iinclude -Ioracle -o $@ $< -Llambdafs_amd -lhrs -Loracle -loracle \
+	    -Wl,-rpath,'$$ORIGIN/../../lambdafs_amd' -Wl,-rpath,'$$ORIGIN/../../oracle'
+
 # The CRC tables the kernels load, dumped for tests/test_crc_tables.py (host code;
 # hipcc only for the HIP headers hrs_crc.hpp includes).
 tests/cpp/crc_tables: tests/cpp/crc_tables.cpp lambdafs_amd/csrc/crc32.hpp lambdafs_amd/csrc/hrs_crc.hpp
@@ -166,7 +182,7 @@ SAN      := -fsanitize=address,undefined -fno-sanitize-recover=undefined -fno-om
 HSAN     := -Xarch_host -fsanitize=address -Xarch_host -fsanitize=undefined -Xarch_host -fno-sanitize-recover=undefined \
             -Xarch_host -fno-omit-frame-pointer
 ASAN_BIN := $(ASAN_DIR)/host_logic $(ASAN_DIR)/jni_harness $(ASAN_DIR)/codec_harness $(ASAN_DIR)/scrub_logic \
-            $(ASAN_DIR)/heal_logic
+            $(ASAN_DIR)/heal_logic $(ASAN_DIR)/heal_erased_logic
 ASAN_LOG := profiles/r06/asan
 
 ASAN_API := $(patsubst %,$(ASAN_DIR)/%.o,$(API_SRC))
@@ -194,6 +210,9 @@ $(ASAN_DIR)/scrub_logic: tests/cpp/scrub_logic.cpp $(ASAN_DIR)/libhrs.so $(ASAN_
 $(ASAN_DIR)/heal_logic: tests/cpp/heal_logic.cpp $(ASAN_DIR)/libhrs.so $(ASAN_DIR)/liboracle.so
 	$(CLANG)++ $(SAN) -std=c++17 -Iinclude -Ioracle -o $@ $< -L$(ASAN_DIR) -lhrs -loracle $(ASAN_RPATH)
 
+$(ASAN_DIR)/heal_erased_logic: tests/cpp/heal_erased_logic.cpp $(ASAN_DIR)/libhrs.so $(ASAN_DIR)/liboracle.so
+	$(CLANG)++ $(SAN) -std=c++17 -Iinclude -Ioracle -o $@ $< -L$(ASAN_DIR) -lhrs -loracle $(ASAN_RPATH)
+
 $(ASAN_DIR)/jni_harness: tests/cpp/jni_harness.c $(ASAN_DIR)/libhrs_jni.so $(ASAN_DIR)/liboracle.so
 	$(CLANG) $(SAN) -std=c11 -Iinclude -Ioracle -o $@ $< -L$(ASAN_DIR) -lhrs_jni -lhrs -loracle -lz -ldl $(ASAN_RPATH)
 
@@ -208,6 +227,7 @@ asan: $(ASAN_BIN)
 	  $(ASAN_DIR)/host_logic; \
 	  $(ASAN_DIR)/scrub_logic; \
 	  $(ASAN_DIR)/heal_logic; \
+	  $(ASAN_DIR)/heal_erased_logic; \
 	  $(ASAN_DIR)/jni_harness --cpu; \
 	  for kp in "10 4" "12 4" "6 3" "3 2"; do $(ASAN_DIR)/codec_harness --host-only $$kp; done' \
 	  > $(ASAN_LOG)/asan_run.log 2>&1 || { cat $(ASAN_LOG)/asan_run.log; exit 1; }
@@ -225,4 +245,4 @@ tsan: tests/cpp/copy_pool_test.cpp lambdafs_amd/csrc/hrs_host.hpp
 clean:
 	rm -rf build $(LIB) $(ORACLE) $(JNI) $(HARNESS) $(TOOLS)
 
-.PHONY: all tsan clean asan scrub_crc_resources
+.PHONY: all tsan clean asan scrub_crc_resources heal_erased_resources

@@ -561,6 +561,89 @@ hrs_status hrs_heal_batch_host(hrs_codec* codec, uint8_t* stripes, size_t row_st
  * the kernels run. report: 4 + n words. len == 0: nothing is touched. */
 hrs_status hrs_heal_host(const hrs_codec* codec, uint8_t* const* rows, size_t len, uint32_t* report);
 
+/* ---- heal with known erasures: repair lost cells and fix survivors ----
+ * hrs_decode_batch_dev rebuilds lost cells from survivors it trusts blindly;
+ * hrs_heal_dev fixes silent errors only while all n cells are present. RS(k,p)
+ * corrects e known erasures and t unknown errors of a column whenever
+ * e + 2 t <= p, and this call does both in one pass. Per byte column, with E
+ * the stripe's erased locations (e <= p, distinct, taken ascending) and
+ * d_l the bytes of the survivors l not in E (bytes stored at erased locations
+ * are never read):
+ *   1. S_i = sum_{l not in E} alpha^(i l) d_l, i < p (erased cells count as 0);
+ *   2. Gamma(x) = prod_{m in E} (1 + alpha^m x) = sum_j Gamma_j x^j and
+ *      T_i = sum_{j <= e} Gamma_j S_{i+e-j}, i < p' = p - e: the erased cells
+ *      add nothing to T, an error u at survivor y adds
+ *      u prod_{m in E} (alpha^y + alpha^m) alpha^(y i);
+ *   3. every T_i zero, or p' = 0: the survivors are consistent, nobody is blamed;
+ *   4. otherwise the column is bad: unresolved if p' < 2, else the locator of
+ *      computeErrorLocations (quirks included) runs on the p' values T; the
+ *      column is resolved when it returns true and blames no erased location,
+ *      and then S is corrected by the errors u_j = err'_j / prod_m (alpha^loc_j + alpha^m);
+ *   5. the erased values v solve sum_{m in E} v_m alpha^(m i) = S_i, i < e,
+ *      over the corrected S of a resolved column and S as it stands otherwise.
+ * Stores: every byte of every erased cell is written with v_m, in every
+ * column; in a resolved column each survivor with u_j != 0 gets ^= u_j (the
+ * heal's rule: a blamed location whose value stands is counted, not stored);
+ * in an unresolved column no survivor is touched, its erased bytes are the
+ * solve over the uncorrected syndromes (defined by this rule, NOT claimed to
+ * equal hrs_decode_batch_dev's bytes there) and it is counted in word 1.
+ * Report, the heal's layout, 4 + n words per stripe:
+ *   word 0 HRS_SCRUB_BAD         columns with a nonzero T
+ *   word 1 HRS_SCRUB_UNRESOLVED  unresolved columns
+ *   word 2 HRS_SCRUB_FIRST_BAD   lowest bad column, or HRS_SCRUB_NONE
+ *   word 3 HRS_SCRUB_PATCHED     survivor bytes stored (the fill of the
+ *                                erased cells is not counted)
+ *   word 4 + l                   resolved columns that blamed survivor l
+ *                                (always 0 for l in E)
+ * Every word is a count or a minimum: scheduling cannot change it.
+ * Three properties follow:
+ *   - e = 0: T = S and Gamma = 1; the call equals hrs_heal_dev byte for byte
+ *     and report word for report word;
+ *   - consistent survivors: the erased cells equal hrs_decode_batch_dev's
+ *     output rows (any k consistent survivors give the same codeword), the
+ *     survivors are unchanged and the report is empty;
+ *   - uniqueness: if the survivors differ from a codeword c in t <= p' / 2
+ *     places and the column comes back resolved, all n bytes equal c: the
+ *     result is a codeword within p' / 2 survivor places of the stored word,
+ *     c is within t of it, and two codewords that differ in at most p'
+ *     survivor places plus e erased places (<= p < p + 1) are one codeword. A
+ *     resolved column within capacity is never miscorrected.
+ * Whether a column within capacity always resolves is the reference
+ * locator's business: it does at parity_size <= 4; at parity_size 8 the
+ * quirky elimination leaves a few such columns unresolved (DESIGN.md section
+ * 10.3). Past capacity the distance limit holds as for the heal; at e = p no
+ * spare is left and every error goes undetected. A caller who cannot accept
+ * that compares CRCs afterwards (hrs_crc32_dev). Codes as for the scrub. */
+
+/* Device-resident batch. rows, stride, len, nstripes, reports, report_stride
+ * and stream as for hrs_heal_dev (n DEVICE pointers, none NULL, no two equal;
+ * cells at erased locations are written, never read). erased: HOST int array
+ * laid out as for hrs_decode_batch_dev, the erased locations of stripe s at
+ * erased[s * max_erased + t] up to the first negative value (or max_erased
+ * entries); a stripe may have none. More than parity_size erasures in a
+ * stripe: HRS_ETOOMANY; a location outside [0, n), a location repeated within
+ * a stripe or max_erased < 0: HRS_EINVAL. Argument errors come before the
+ * device is selected (HRS_EDEVICE for a host-only handle). len == 0 or
+ * nstripes == 0 touches nothing; max_erased == 0 is hrs_heal_dev. The
+ * stripes' erasure sets are de-duplicated into a device table (any number of
+ * distinct patterns). 16-byte aligned rows and stride take
+ * heal_erased_kernel<P> over the whole 2 KiB windows (every parity size 1..8
+ * is built without scratch memory; none is routed away); the row tail,
+ * unaligned layouts and kernel mode 2 take heal_erased_bytewise_kernel<P>
+ * (hrs_last_kernel names them by the scrub's tail rule). Asynchronous on
+ * stream. */
+hrs_status hrs_heal_erased_dev(hrs_codec* codec, uint8_t* const* rows, size_t stride, size_t len, size_t nstripes,
+                               const int* erased, int max_erased, uint32_t* reports, size_t report_stride,
+                               void* stream);
+
+/* The same operation for one stripe of n HOST rows on the CPU (works on
+ * HRS_DEVICE_NONE handles): a plain loop over the columns through the locator
+ * the kernels run, their byte-exact reference. erased[num_erased]: the
+ * stripe's erased locations (read up to the first negative value). report:
+ * 4 + n words. len == 0: nothing is touched. */
+hrs_status hrs_heal_erased_host(const hrs_codec* codec, uint8_t* const* rows, size_t len, const int* erased,
+                                int num_erased, uint32_t* report);
+
 /* ---- scrub and heal + CRC-32: the block checksums in the same pass ----
  * In the reference system a bad cell is first known by its block checksum
  * (Encoder.java:408-450 stores one per block; Decoder.java:373-387 turns a

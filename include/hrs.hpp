@@ -352,6 +352,27 @@ class HipReedSolomonCode : public HipCode {
       throw std::invalid_argument("healHost: row count does not match the codec");
     check(hrs_heal_host(h_, rows.data(), len, report), h_);
   }
+
+  // Heal with known erasures (hrs_heal_erased_dev): per stripe the lost cells
+  // listed in the HOST array erased[nstripes * maxErased] (negative = end of a
+  // stripe's list) are rebuilt and the silent errors of the survivors fixed,
+  // in one pass; reports as for healDev. Asynchronous on stream.
+  void healErasedDev(const std::vector<uint8_t*>& rows, size_t stride, size_t len, size_t nstripes, const int* erased,
+                     int maxErased, uint32_t* reports, size_t reportStride, void* stream = nullptr) {
+    if (static_cast<int>(rows.size()) != stripeSize() + paritySize())
+      throw std::invalid_argument("healErasedDev: row count does not match the codec");
+    check(hrs_heal_erased_dev(h_, rows.data(), stride, len, nstripes, erased, maxErased, reports, reportStride, stream),
+          h_);
+  }
+
+  // One stripe of n host rows on the CPU (hrs_heal_erased_host; host-only
+  // handles included); report holds HRS_SCRUB_HEAD + n words.
+  void healErasedHost(const std::vector<uint8_t*>& rows, size_t len, const std::vector<int>& erased,
+                      uint32_t* report) {
+    if (static_cast<int>(rows.size()) != stripeSize() + paritySize())
+      throw std::invalid_argument("healErasedHost: row count does not match the codec");
+    check(hrs_heal_erased_host(h_, rows.data(), len, erased.data(), static_cast<int>(erased.size()), report), h_);
+  }
 };
 
 class HipXORCode : public HipCode {

@@ -245,6 +245,20 @@ hrs_status upload_batch_plans(hrs_codec* c, const BatchPlanSet& ps, hipStream_t 
                               const hrs::BatchPlan** dplans, const int32_t** dpat) {
   const size_t plan_bytes = ps.plans.size() * sizeof(hrs::BatchPlan);
   const size_t need = plan_bytes + ps.pat.size() * sizeof(int32_t);
+  hrs_status st = batch_slot_acquire(c, need, slot);
+  if (st != HRS_OK) return st;
+  hrs_codec::BatchSlot& sl = **slot;
+  std::memcpy(sl.host, ps.plans.data(), plan_bytes);
+  std::memcpy(sl.host + plan_bytes, ps.pat.data(), ps.pat.size() * sizeof(int32_t));
+  hipError_t e = hipMemcpyAsync(sl.dev, sl.host, need, hipMemcpyHostToDevice, hs);
+  if (e != hipSuccess) return hip_fail(c, e, "hipMemcpyAsync plans");
+  *dplans = reinterpret_cast<const hrs::BatchPlan*>(sl.dev);
+  *dpat = reinterpret_cast<const int32_t*>(sl.dev + plan_bytes);
+  return HRS_OK;
+}
+
+// The next batch slot, idle and at least `need` bytes on both sides.
+hrs_status batch_slot_acquire(hrs_codec* c, size_t need, hrs_codec::BatchSlot** slot) {
   hrs_codec::BatchSlot& sl = c->batch[c->batch_next];
   c->batch_next ^= 1;
   if (sl.pending) {
@@ -269,13 +283,7 @@ hrs_status upload_batch_plans(hrs_codec* c, const BatchPlanSet& ps, hipStream_t 
     if (e != hipSuccess) return fail(c, HRS_ENOMEM, "hipHostMalloc(%zu): %s", bytes, hipGetErrorString(e));
     sl.bytes = bytes;
   }
-  std::memcpy(sl.host, ps.plans.data(), plan_bytes);
-  std::memcpy(sl.host + plan_bytes, ps.pat.data(), ps.pat.size() * sizeof(int32_t));
-  hipError_t e = hipMemcpyAsync(sl.dev, sl.host, need, hipMemcpyHostToDevice, hs);
-  if (e != hipSuccess) return hip_fail(c, e, "hipMemcpyAsync plans");
   *slot = &sl;
-  *dplans = reinterpret_cast<const hrs::BatchPlan*>(sl.dev);
-  *dpat = reinterpret_cast<const int32_t*>(sl.dev + plan_bytes);
   return HRS_OK;
 }
 

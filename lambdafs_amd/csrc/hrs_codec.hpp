@@ -284,6 +284,13 @@ hrs_status run_scrub_crc(hrs_codec* c, const uint8_t* const* rows, size_t stride
 // kernel mode 0 or 3.
 bool scrub_crc_one_pass(const hrs_codec* c, const uint8_t* const* rows, size_t stride, size_t len);
 
+// ---- per-call device tables (hrs_batch_api.cpp)
+// The next of the handle's two batch slots (pinned staging `host` + device
+// buffer `dev`, each at least `need` bytes), waited idle. The caller fills
+// host, copies it to dev on its stream, and after its launches records
+// slot->done there and sets slot->pending.
+hrs_status batch_slot_acquire(hrs_codec* c, size_t need, hrs_codec::BatchSlot** slot);
+
 // ---- shared by the CRC entry points
 // crc_out may be crc_in itself; any other overlap of the two n-word arrays is refused (hrs_batch_api.cpp).
 bool crc_arrays_apart(const uint32_t* crc_in, const uint32_t* crc_out, size_t n);

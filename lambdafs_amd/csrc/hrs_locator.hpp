@@ -131,5 +131,106 @@ HRS_HD inline bool locate(const Field& f, int n, int p, const uint8_t* s, int* n
   return true;
 }
 
+// ---- errors and erasures together (hrs_heal_erased_*, include/hrs.h)
+//
+// A column of which the e locations eloc[0..e) (ascending, distinct) are lost
+// and the other n - e bytes may carry silent errors. s[0..p) are the syndromes
+// of the survivors alone (erased cells counted as zero). With the erasure
+// locator Gamma(x) = prod_m (1 + alpha^eloc[m] x) = sum_j gamma[j] x^j the
+// modified syndromes T_i = sum_{j <= e} gamma[j] s[i + e - j], i < p - e, hold
+// no term of an erased cell: an error u at survivor y adds
+// u prod_m (alpha^y + alpha^eloc[m]) alpha^(y i), an error-only syndrome
+// sequence of length p - e that locate() takes as it is.
+
+constexpr int kMaxErased = kMaxSyndromes;
+
+enum Errata : int {
+  kConsistent = 0,  // every T_i is 0 (or p - e = 0): nobody is blamed
+  kResolved = 1,    // locate() returned true and blamed survivors only
+  kUnresolved = 2,  // the survivors disagree and cannot be told apart
+};
+
+// gamma[0..e] of the erased set.
+HRS_HD inline void erasure_locator(const Field& f, int e, const uint8_t* eloc, uint8_t* gamma) {
+  gamma[0] = 1;
+  for (int m = 0; m < e; ++m) {
+    const uint8_t x = f.exp[eloc[m]];
+    gamma[m + 1] = 0;
+    for (int j = m + 1; j > 0; --j) gamma[j] ^= fmul(f, gamma[j - 1], x);
+  }
+}
+
+// locate() over the pp modified syndromes t, pp in [2, P]: one call per
+// value, so that each sees a compile-time syndrome count as the scrub's call
+// does (its loops unroll and its matrix stays in registers on the device).
+template <int PP>
+HRS_HD inline bool locate_modified(const Field& f, int n, int pp, const uint8_t* t, int* nloc, uint8_t* loc,
+                                   uint8_t* err) {
+  if constexpr (PP < 2) {
+    return false;
+  } else {
+    if (pp == PP) return locate(f, n, PP, t, nloc, loc, err);
+    return locate_modified<PP - 1>(f, n, pp, t, nloc, loc, err);
+  }
+}
+
+// What locate() is to an error-only column: fills the survivors blamed
+// (loc[0..*nloc) ascending, their error values u[j], the byte at loc[j] is
+// wrong by u[j]; kResolved only) and the e erased values v[m] at eloc[m]:
+// the solution of sum_m v[m] alpha^(eloc[m] i) = s'_i, i < e, over the
+// syndromes s' corrected by the blamed errors (kResolved) or s as it stands
+// (kConsistent, kUnresolved). e <= p <= kMaxSyndromes; gamma from
+// erasure_locator. e = 0 is locate() itself. P = p, the code's parity size.
+template <int P>
+HRS_HD inline int locate_errata(const Field& f, int n, const uint8_t* s, int e, const uint8_t* eloc,
+                                const uint8_t* gamma, int* nloc, uint8_t* loc, uint8_t* u, uint8_t* v) {
+  const int pp = P - e;
+  uint8_t c[kMaxSyndromes];  // the syndromes the erased values are solved from
+  for (int i = 0; i < P; ++i) c[i] = s[i];
+  uint8_t t[kMaxSyndromes];
+  uint32_t nz = 0;
+  for (int i = 0; i < pp; ++i) {
+    uint8_t x = 0;
+    for (int j = 0; j <= e; ++j) x ^= fmul(f, gamma[j], s[i + e - j]);
+    t[i] = x;
+    nz |= x;
+  }
+  int state = kConsistent;
+  *nloc = 0;
+  if (nz != 0) {
+    state = kUnresolved;
+    if (pp >= 2) {
+      int found = 0;
+      bool ok = locate_modified<P>(f, n, pp, t, &found, loc, u);
+      for (int j = 0; j < found; ++j)
+        for (int m = 0; m < e; ++m) ok &= loc[j] != eloc[m];
+      if (ok) {
+        state = kResolved;
+        *nloc = found;
+        for (int j = 0; j < found; ++j) {
+          const uint8_t y = f.exp[loc[j]];
+          uint8_t scale = 1;
+          for (int m = 0; m < e; ++m) scale = fmul(f, scale, static_cast<uint8_t>(y ^ f.exp[eloc[m]]));
+          u[j] = fdiv(f, u[j], scale);
+          for (int i = 0; i < e; ++i) c[i] ^= fmul(f, u[j], fpow(f, static_cast<int>(loc[j]) * i));
+        }
+      }
+    }
+  }
+  // the Vandermonde solve of locate(), over the erased locations
+  uint8_t x[kMaxErased];
+  for (int m = 0; m < e; ++m) {
+    x[m] = f.exp[eloc[m]];
+    v[m] = c[m];
+  }
+  for (int i = 0; i < e - 1; ++i)
+    for (int j = e - 1; j > i; --j) v[j] ^= fmul(f, x[i], v[j - 1]);
+  for (int i = e - 1; i >= 0; --i) {
+    for (int j = i + 1; j < e; ++j) v[j] = fdiv(f, v[j], static_cast<uint8_t>(x[j] ^ x[j - i - 1]));
+    for (int j = i; j < e - 1; ++j) v[j] ^= v[j + 1];
+  }
+  return state;
+}
+
 }  // namespace locator
 }  // namespace hrs

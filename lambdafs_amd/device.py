@@ -456,6 +456,99 @@ def heal_batch_host(code, stripes):
     return reports
 
 
+def heal_host(code, rows):
+    """hrs_heal_host: one stripe of n HOST rows (contiguous writable uint8
+    numpy arrays of one length, hops order) healed in place on the CPU; works
+    on host-only handles. Returns the report, a numpy uint32 array [4 + n]."""
+    n = code.stripeSize() + code.paritySize()
+    L = _host_stripe_rows(rows, n)
+    report = np.zeros(SCRUB_HEAD + n, dtype=np.uint32)
+    report[SCRUB_FIRST_BAD] = SCRUB_NONE
+    code._check(_lib.lib().hrs_heal_host(code._handle(), _lib.ptr_array([r.ctypes.data for r in rows]), L,
+                                         report.ctypes.data))
+    return report
+
+
+def _host_stripe_rows(rows, n):
+    if len(rows) != n:
+        raise ValueError(f"need {n} rows")
+    for r in rows:
+        if not (isinstance(r, np.ndarray) and r.dtype == np.uint8 and r.ndim == 1 and r.flags.c_contiguous
+                and r.flags.writeable and len(r) == len(rows[0])):
+            raise ValueError("rows must be contiguous writable uint8 numpy arrays of one length")
+    return len(rows[0])
+
+
+def _erased_array(erased, S, what="erased"):
+    """The host int32 [S, max_erased] erasure array of hrs_heal_erased_dev from
+    a [S, m] array or a list of per-stripe location lists (-1 padded)."""
+    torch = _lib.torch
+    if torch is not None and isinstance(erased, torch.Tensor):
+        erased = erased.cpu().numpy()
+    if isinstance(erased, np.ndarray):
+        arr = np.ascontiguousarray(erased.astype(np.int32))
+        if arr.ndim != 2 or arr.shape[0] != S:
+            raise ValueError(f"{what} must be [S, max_erased]")
+        return arr
+    lists = [list(e) for e in erased]
+    if len(lists) != S:
+        raise ValueError(f"{what} must list the erased locations of each of the {S} stripes")
+    arr = np.full((S, max(1, max(len(e) for e in lists))), -1, dtype=np.int32)
+    for s, e in enumerate(lists):
+        arr[s, : len(e)] = e
+    return arr
+
+
+def _heal_erased(code, rows, stride, L, S, ref, erased):
+    torch = _lib.torch
+    n = code.stripeSize() + code.paritySize()
+    arr = _erased_array(erased, S)
+    reports = torch.empty((S, SCRUB_HEAD + n), dtype=torch.int32, device=ref.device)
+    code._check(_lib.lib().hrs_heal_erased_dev(code._handle(), rows, stride, L, S, arr.ctypes.data, arr.shape[1],
+                                               reports.data_ptr(), SCRUB_HEAD + n, _stream(ref)))
+    return reports
+
+
+def heal_erased_stripes(code, stripes, erased):
+    """Heal with known erasures (hrs_heal_erased_dev) over stripes[S, n, L]:
+    per stripe the lost cells erased[s] (an int [S, m] array, -1 padded, e.g.
+    from checksums_to_erased, or a list of location lists; a stripe may have
+    none) are rebuilt in place from the survivors, and silent errors in the
+    survivors are located and fixed in the same pass wherever
+    erasures + 2 * errors <= p per column. Returns the reports [S, 4 + n] in the
+    heal's layout: columns whose survivors disagree, unresolved columns, first
+    bad column, survivor bytes stored, then per survivor the resolved columns
+    that blamed it."""
+    n = code.stripeSize() + code.paritySize()
+    if stripes.dim() != 3 or stripes.shape[1] != n:
+        raise ValueError(f"stripes must be [S, {n}, L]")
+    rows, stride, L, S = _stripe_rows(stripes, range(n))
+    return _heal_erased(code, rows, stride, L, S, stripes, erased)
+
+
+def heal_erased_rows(code, row_views, erased):
+    """heal_erased_stripes with explicit [S, L] row views, one per location in hops order."""
+    n = code.stripeSize() + code.paritySize()
+    if len(row_views) != n or any(v is None for v in row_views):
+        raise ValueError(f"need {n} row views")
+    rows, stride, L, S = _rows(row_views)
+    return _heal_erased(code, rows, stride, L, S, row_views[0], erased)
+
+
+def heal_erased_host(code, rows, erased):
+    """hrs_heal_erased_host: heal_erased_stripes for one stripe of n HOST rows
+    (as for heal_host) on the CPU, the kernels' byte-exact reference; works on
+    host-only handles. Returns the report, a numpy uint32 array [4 + n]."""
+    n = code.stripeSize() + code.paritySize()
+    L = _host_stripe_rows(rows, n)
+    erased = [int(e) for e in erased]
+    report = np.zeros(SCRUB_HEAD + n, dtype=np.uint32)
+    report[SCRUB_FIRST_BAD] = SCRUB_NONE
+    code._check(_lib.lib().hrs_heal_erased_host(code._handle(), _lib.ptr_array([r.ctypes.data for r in rows]), L,
+                                                _lib.int_array(erased), len(erased), report.ctypes.data))
+    return report
+
+
 def scrub_to_erased(reports, p):
     """The int32 [S, p] erasure array decode_batch takes from scrub reports
     [S, 4 + n]: per stripe the locations with a nonzero count, ascending, -1
