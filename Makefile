@@ -11,11 +11,12 @@ PROBE    := lambdafs_amd/libhrs_probe.so
 ORACLE   := oracle/liboracle.so
 HDRS     := Makefile include/hrs.h lambdafs_amd/csrc/hrs_device.hpp lambdafs_amd/csrc/hrs_launch.hpp lambdafs_amd/csrc/gf256.hpp lambdafs_amd/csrc/hrs_internal.hpp \
             lambdafs_amd/csrc/crc32.hpp lambdafs_amd/csrc/hrs_crc.hpp lambdafs_amd/csrc/xor_sched.hpp lambdafs_amd/csrc/hrs_codec.hpp \
-            lambdafs_amd/csrc/hrs_host.hpp lambdafs_amd/csrc/hrs_locator.hpp lambdafs_amd/csrc/hrs_heal_erased.hpp
+            lambdafs_amd/csrc/hrs_host.hpp lambdafs_amd/csrc/hrs_locator.hpp lambdafs_amd/csrc/hrs_heal_erased.hpp \
+            lambdafs_amd/csrc/hrs_scrub_device.hpp
 
 # Host translation units of the C ABI (no kernels): lifecycle + queries,
 # matrices, device dispatch + CRC, host-buffer path, batches, scrubbing.
-API_SRC  := hrs_api hrs_matrix hrs_dispatch hrs_hostpath hrs_batch_api hrs_scrub_api hrs_heal_erased_api
+API_SRC  := hrs_api hrs_matrix hrs_dispatch hrs_hostpath hrs_batch_api hrs_scrub_api
 API_OBJ  := $(patsubst %,build/%.o,$(API_SRC))
 
 JNI      := lambdafs_amd/libhrs_jni.so
@@ -43,70 +44,25 @@ $(API_OBJ): build/%.o: lambdafs_amd/csrc/%.cpp $(HDRS)
 	@mkdir -p build
 	$(HIPCC) $(HIPFLAGS) -x hip -c $< -o $@
 
-build/hrs_kernels.o: lambdafs_amd/csrc/hrs_kernels.hip $(HDRS)
-	@mkdir -p build
-	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-
-build/hrs_runtime.o: lambdafs_amd/csrc/hrs_runtime.hip $(HDRS)
-	@mkdir -p build
-	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-
-build/hrs_batch.o: lambdafs_amd/csrc/hrs_batch.hip $(HDRS)
-	@mkdir -p build
-	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-
-build/hrs_crc.o: lambdafs_amd/csrc/hrs_crc.hip $(HDRS)
+# The kernel translation units, one code object each.
+build/%.o: lambdafs_amd/csrc/%.hip $(HDRS)
 	@mkdir -p build
 	$(HIPCC) $(HIPFLAGS) -c $< -o $@
 
 # The fused kernels' XOR networks and CRC steps must unroll completely (a
 # K = 12 network otherwise stays a loop of runtime mask tests, 5x slower):
 # lift the pragma-unroll size cap for this file.
-build/hrs_fused.o: lambdafs_amd/csrc/hrs_fused.hip $(HDRS)
-	@mkdir -p build
-	$(HIPCC) $(HIPFLAGS) -mllvm -pragma-unroll-threshold=1000000 -c $< -o $@
+build/hrs_fused.o: HIPFLAGS += -mllvm -pragma-unroll-threshold=1000000
 
-build/hrs_decode_crc.o: lambdafs_amd/csrc/hrs_decode_crc.hip $(HDRS)
-	@mkdir -p build
-	$(HIPCC) $(HIPFLAGS) -c $< -o $@
+build/hrs_probe.o: include/hrs_probe.h
 
-build/hrs_batch_crc.o: lambdafs_amd/csrc/hrs_batch_crc.hip $(HDRS)
+# `make scrub_resources`, `make scrub_crc_resources`, `make heal_erased_resources`:
+# the compiler's resource report of every kernel of hrs_<name>.hip (the scrub
+# family carries no scratch). Not .PHONY: a phony target takes no pattern rule.
+%_resources: lambdafs_amd/csrc/hrs_%.hip $(HDRS)
 	@mkdir -p build
-	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-
-build/hrs_gate.o: lambdafs_amd/csrc/hrs_gate.hip $(HDRS)
-	@mkdir -p build
-	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-
-build/hrs_scrub.o: lambdafs_amd/csrc/hrs_scrub.hip $(HDRS)
-	@mkdir -p build
-	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-
-# scrub / heal + CRC-32 in one pass. `make scrub_crc_resources` prints the
-# compiler's resource report of every fused instantiation (no scratch allowed).
-build/hrs_scrub_crc.o: lambdafs_amd/csrc/hrs_scrub_crc.hip $(HDRS)
-	@mkdir -p build
-	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-
-scrub_crc_resources: lambdafs_amd/csrc/hrs_scrub_crc.hip $(HDRS)
-	@mkdir -p build
-	$(HIPCC) $(HIPFLAGS) -Rpass-analysis=kernel-resource-usage -c $< -o build/hrs_scrub_crc.report.o 2>&1 | \
-	    grep -E 'Function Name|VGPRs:|ScratchSize|Occupancy|LDS Size'
-
-# Heal with known erasures. `make heal_erased_resources` prints the compiler's
-# resource report of every instantiation (no scratch allowed).
-build/hrs_heal_erased.o: lambdafs_amd/csrc/hrs_heal_erased.hip $(HDRS)
-	@mkdir -p build
-	$(HIPCC) $(HIPFLAGS) -c $< -o $@
-
-heal_erased_resources: lambdafs_amd/csrc/hrs_heal_erased.hip $(HDRS)
-	@mkdir -p build
-	$(HIPCC) $(HIPFLAGS) -Rpass-analysis=kernel-resource-usage -c $< -o build/hrs_heal_erased.report.o 2>&1 | \
-	    grep -E 'Function Name|VGPRs:|ScratchSize|Occupancy|LDS Size'
-
-build/hrs_probe.o: lambdafs_amd/csrc/hrs_probe.hip include/hrs_probe.h $(HDRS)
-	@mkdir -p build
-	$(HIPCC) $(HIPFLAGS) -c $< -o $@
+	$(HIPCC) $(HIPFLAGS) -Rpass-analysis=kernel-resource-usage -c $< -o build/hrs_$*.report.o 2>&1 | \
+	    grep -E 'Function Name|VGPRs:|SGPRs:|ScratchSize|Occupancy|LDS Size'
 
 KOBJ     := build/hrs_kernels.o build/hrs_runtime.o build/hrs_batch.o build/hrs_crc.o build/hrs_fused.o build/hrs_decode_crc.o \
             build/hrs_batch_crc.o build/hrs_gate.o build/hrs_scrub.o build/hrs_scrub_crc.o build/hrs_heal_erased.o
@@ -245,4 +201,4 @@ tsan: tests/cpp/copy_pool_test.cpp lambdafs_amd/csrc/hrs_host.hpp
 clean:
 	rm -rf build $(LIB) $(ORACLE) $(JNI) $(HARNESS) $(TOOLS)
 
-.PHONY: all tsan clean asan scrub_crc_resources heal_erased_resources
+.PHONY: all tsan clean asan

@@ -1045,13 +1045,8 @@ hrs_status scrub_batch_host_entry(hrs_codec* c, const uint8_t* stripes, size_t r
                                   size_t len, size_t nstripes, uint32_t* reports, size_t report_stride, bool heal,
                                   bool with_crc = false, const uint32_t* crc_in = nullptr,
                                   uint32_t* crc_out = nullptr) {
-  if (!c) return HRS_EINVAL;
-  hrs_status st = scrub_code_ok(c, report_stride, true);
-  if (st != HRS_OK) return st;
-  if (!stripes || !reports) return fail(c, HRS_EINVAL, "stripes or reports is NULL");
-  if (nstripes > 0x7fffffffu) return fail(c, HRS_EINVAL, "too many stripes");
-  if (len > 0xffffffffu) return fail(c, HRS_EINVAL, "rows of %zu bytes: column indices are 32-bit", len);
-  if (nstripes == 0 || len == 0) return HRS_OK;
+  hrs_status st = scrub_args_ok(c, stripes, reports, report_stride, len, nstripes, kScrubWithReports | kScrubImage);
+  if (st != HRS_OK || nstripes == 0 || len == 0) return st;
   // A read-only pass over a mis-strided batch would report "clean" or "bad"
   // with no error: the cells must not overlap. Rows of a stripe packed inside
   // the stripe stride, or stripes of a row packed inside the row stride.

@@ -264,6 +264,20 @@ bool apply_crc_one_pass(const hrs_codec* c, int nout, int nlive, size_t len);
 // The code and report_stride checks of the scrub entry points (rs only,
 // p <= 8, report_stride >= 4 + n when with_reports).
 hrs_status scrub_code_ok(hrs_codec* c, size_t report_stride, bool with_reports);
+// The argument rules every scrub / heal entry point shares, in this order: the
+// handle (NULL: HRS_EINVAL, no message), scrub_code_ok, `cells` and `reports`
+// not NULL, the n row pointers `cells` holds, the erased list when
+// `erased_what` names its count ("max_erased %d with no erased list"), then
+// nstripes < 2^31 and len < 2^32. The empty batch and the device are the
+// caller's.
+enum : unsigned {
+  kScrubWithReports = 1u,  // one report per stripe: report_stride is checked ("reports"; else one "report")
+  kScrubRowsWritten = 2u,  // the rows are written: heal_rows_ok instead of the NULL check of each row
+  kScrubImage = 4u,        // `cells` is one batch image ("stripes") with no row pointers to check
+};
+hrs_status scrub_args_ok(hrs_codec* c, const void* cells, const uint32_t* reports, size_t report_stride, size_t len,
+                         size_t nstripes, unsigned flags, const char* erased_what = nullptr, int erased_count = 0,
+                         const int* erased = nullptr);
 // Empty reports, then the vector kernel over the whole 2 KiB windows and the
 // byte-granular kernel over the rest, all on stream s. rows[n]: none NULL.
 // heal: the kernels' heal variants, which also write the resolved columns

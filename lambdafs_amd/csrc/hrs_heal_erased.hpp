@@ -1,5 +1,5 @@
 // Heal with known erasures (hrs_heal_erased_dev, include/hrs.h): the interface
-// between the host unit (hrs_heal_erased_api.cpp) and the kernels
+// between the host unit (hrs_scrub_api.cpp) and the kernels
 // (hrs_heal_erased.hip).
 #pragma once
 #include <hip/hip_runtime.h>

@@ -7,6 +7,7 @@
 #include <cstdint>
 #include <cstdlib>
 #include <string>
+#include <type_traits>
 
 #include "hrs_internal.hpp"
 
@@ -26,6 +27,29 @@ inline void note_kernel_t(const char* base, T... v) {
     s += '>';
   }
   note_kernel(s.c_str());
+}
+
+// The parity size as a template argument: f(std::integral_constant<int, p>)
+// for p in [Lo, Hi], hipErrorInvalidValue outside. f returns a hipError_t
+// (the launchers) or nothing (host loops: hipSuccess). The call of f stands
+// before the recursion, so the kernels it names are instantiated in ascending
+// p, the order of the case ladders this replaces.
+template <int Lo, int Hi, class F>
+inline hipError_t dispatch_p(int p, F&& f) {
+  if constexpr (Lo > Hi) {
+    return hipErrorInvalidValue;
+  } else {
+    constexpr std::integral_constant<int, Lo> P{};
+    if (p == Lo) {
+      if constexpr (std::is_void_v<decltype(f(P))>) {
+        f(P);
+        return hipSuccess;
+      } else {
+        return f(P);
+      }
+    }
+    return dispatch_p<Lo + 1, Hi>(p, f);
+  }
 }
 
 // CU count per device, cached; handles on several host threads may race to

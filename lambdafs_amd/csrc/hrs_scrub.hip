@@ -15,55 +15,22 @@
 //
 // Every report word is a count or a minimum, added with atomics, so the
 // result does not depend on how the windows were scheduled.
+//
+// This file holds the window loop, the byte-granular loop and the launchers.
+// The Horner step, the walk over a dirty window's columns, the report rule of
+// one bad column (count_column -> account_column), the per-wave histogram and
+// the field tables are hrs_scrub_device.hpp's, shared with hrs_scrub_crc.hip.
 #include <hip/hip_runtime.h>
 
 #include "hrs_device.hpp"
 #include "hrs_launch.hpp"
 #include "hrs_locator.hpp"
+#include "hrs_scrub_device.hpp"
 
 namespace hrs {
 namespace {
 
-__constant__ gf::Tables d_scrub_tables = gf::make_tables();
-
 constexpr int kScrubGroup = 8;  // rows of a window in flight per wave (8 x 2 KiB)
-
-__device__ __forceinline__ void load_tables(uint8_t* s_exp, uint8_t* s_log) {
-  for (int i = threadIdx.x; i < 512; i += blockDim.x) s_exp[i] = d_scrub_tables.exp[i];
-  for (int i = threadIdx.x; i < 256; i += blockDim.x) s_log[i] = d_scrub_tables.log[i];
-}
-
-// One bad column (syndromes s, not all zero) into the counters at h: a
-// per-wave LDS histogram (vector kernel) or the stripe's report itself.
-// Heal: a resolved column is also written back, data[loc[j]] ^= err[j] at
-// rows[loc[j]] + at (ReedSolomonCode.java:281-285), one byte load, XOR and
-// byte store per nonzero error value, counted in word 3. An unresolved column
-// is not touched (the Java returns false after writing it; include/hrs.h).
-// The column belongs to this lane alone, so the stores race with nothing.
-template <int P, bool Heal>
-__device__ __forceinline__ void count_column(const locator::Field& f, int n, const uint8_t (&s)[P], uint32_t col,
-                                             uint32_t* h, const uint8_t* const* rows, uint64_t at) {
-  int nloc = 0;
-  uint8_t loc[locator::kMaxErrors], err[locator::kMaxErrors];
-  const bool resolved = locator::locate(f, n, P, s, &nloc, loc, err);
-  atomicAdd(&h[0], 1u);
-  atomicMin(&h[2], col);
-  if (!resolved) {
-    atomicAdd(&h[1], 1u);
-  } else {
-    for (int j = 0; j < nloc; ++j) atomicAdd(&h[kScrubHead + loc[j]], 1u);
-    if constexpr (Heal) {
-      uint32_t patched = 0u;
-      for (int j = 0; j < nloc; ++j)
-        if (err[j] != 0) {
-          uint8_t* q = const_cast<uint8_t*>(rows[loc[j]]) + at;
-          *q = static_cast<uint8_t>(*q ^ err[j]);
-          ++patched;
-        }
-      if (patched != 0u) atomicAdd(&h[kScrubPatched], patched);
-    }
-  }
-}
 
 // ------------------------------------------------------ vector kernel
 
@@ -76,12 +43,9 @@ __global__ void __launch_bounds__(kBlockThreads) scrub_kernel(const ScrubArgs a)
   __shared__ uint8_t s_exp[512];
   __shared__ uint8_t s_log[256];
   __shared__ uint32_t s_hist[kWavesPerBlock][kScrubHead + kScrubMaxRows];
-  load_tables(s_exp, s_log);
+  load_field_tables(s_exp, s_log, blockDim.x);
   const int nwords = kScrubHead + a.n;
-  for (int i = threadIdx.x; i < kWavesPerBlock * (kScrubHead + kScrubMaxRows); i += blockDim.x) {
-    const int e = i % (kScrubHead + kScrubMaxRows);
-    s_hist[i / (kScrubHead + kScrubMaxRows)][e] = e == 2 ? kScrubNone : 0u;
-  }
+  hist_init(&s_hist[0][0], kScrubHead + kScrubMaxRows, kWavesPerBlock);
   __syncthreads();
   const locator::Field f{s_exp, s_log};
   const int lane = threadIdx.x & 63;
@@ -107,13 +71,7 @@ __global__ void __launch_bounds__(kBlockThreads) scrub_kernel(const ScrubArgs a)
       for (int g = 0; g < kScrubGroup; ++g)
         if (l0 - 1 - g >= 0) {
           bitslice(w[g]);
-#pragma unroll
-          for (int i = 0; i < P; ++i) {
-#pragma unroll
-            for (int r = 0; r < i; ++r) xtime(acc[i]);
-#pragma unroll
-            for (int q = 0; q < 8; ++q) acc[i][q] ^= w[g][q];
-          }
+          horner_sliced<P>(acc, w[g]);
         }
     }
     uint32_t any = 0u;
@@ -123,53 +81,16 @@ __global__ void __launch_bounds__(kBlockThreads) scrub_kernel(const ScrubArgs a)
       for (int q = 0; q < 8; ++q) any |= acc[i][q];
     if (__ballot(any != 0u) == 0ull) continue;  // clean window (wave-uniform)
 
-    // slow path: the lane's 32 columns are bytes 0..3 of words 0..7 of the
-    // un-sliced syndromes; word x covers window bytes (x >> 2) * 1024 + lane * 16 + (x & 3) * 4
+    // slow path: un-slice the syndromes and run the locator on the lane's bad columns
 #pragma unroll
     for (int i = 0; i < P; ++i) bitslice(acc[i]);
     if (any != 0u) {
-#pragma unroll 1
-      for (int x = 0; x < 8; ++x) {
-        uint32_t cur[P];
-#pragma unroll
-        for (int i = 0; i < P; ++i) {
-          uint32_t v = acc[i][0];
-#pragma unroll
-          for (int q = 1; q < 8; ++q) v = (x == q) ? acc[i][q] : v;  // selects, so acc stays in registers
-          cur[i] = v;
-        }
-        uint32_t anyw = 0u;
-#pragma unroll
-        for (int i = 0; i < P; ++i) anyw |= cur[i];
-        if (anyw == 0u) continue;
-#pragma unroll 1
-        for (int b = 0; b < 4; ++b) {
-          uint8_t s[P];
-          uint32_t nz = 0u;
-#pragma unroll
-          for (int i = 0; i < P; ++i) {
-            s[i] = static_cast<uint8_t>(cur[i] >> (8 * b));
-            nz |= s[i];
-          }
-          if (nz == 0u) continue;
-          const uint32_t col = static_cast<uint32_t>(off) + (x >> 2) * 1024u + lane * 16u + (x & 3) * 4u + b;
-          count_column<P, Heal>(f, a.n, s, col, hist, a.rows, stripe * a.stride + col);
-        }
-      }
+      auto column = [&](const uint8_t(&s)[P], uint32_t col, int, int) {
+        count_column<P, Heal>(f, a.n, s, col, hist, a.rows, stripe * a.stride + col);
+      };
+      for_each_bad_column<P>(acc, static_cast<uint32_t>(off), lane, column);
     }
-    // flush this window's counts to its stripe (a wave's consecutive windows
-    // can belong to different stripes); the exchange re-arms the histogram
-    __builtin_amdgcn_wave_barrier();
-    uint32_t* rep = a.reports + stripe * a.report_stride;
-    for (int e = lane; e < nwords; e += 64) {
-      const uint32_t v = atomicExch(&hist[e], e == 2 ? kScrubNone : 0u);
-      if (e == 2) {
-        if (v != kScrubNone) atomicMin(&rep[2], v);
-      } else if (v != 0u) {
-        atomicAdd(&rep[e], v);
-      }
-    }
-    __builtin_amdgcn_wave_barrier();
+    hist_flush(hist, a.reports + stripe * a.report_stride, nwords, lane);
   }
 }
 
@@ -182,25 +103,21 @@ template <int P, bool Heal = false>
 __global__ void __launch_bounds__(kBlockThreads) scrub_bytewise_kernel(const ScrubArgs a) {
   __shared__ uint8_t s_exp[512];
   __shared__ uint8_t s_log[256];
-  load_tables(s_exp, s_log);
+  load_field_tables(s_exp, s_log, blockDim.x);
   __syncthreads();
   const locator::Field f{s_exp, s_log};
-  const uint64_t wlen = a.len - a.col0;
   const uint64_t nthreads = static_cast<uint64_t>(gridDim.x) * blockDim.x;
   for (uint64_t idx = static_cast<uint64_t>(blockIdx.x) * blockDim.x + threadIdx.x; idx < a.ntasks;
        idx += nthreads) {
-    const uint64_t stripe = idx / wlen;
-    const uint64_t col = a.col0 + (idx - stripe * wlen);
-    const uint64_t at = stripe * a.stride + col;
+    const BytewiseTask t = bytewise_task(a, idx);
     uint8_t s[P];
-#pragma unroll
-    for (int i = 0; i < P; ++i) s[i] = 0;
-    for (int l = a.n - 1; l >= 0; --l) locator::horner_step<P>(f, s, a.rows[l][at]);
+    bytewise_syndromes<P>(f, a, t.at, s);
     uint32_t nz = 0u;
 #pragma unroll
     for (int i = 0; i < P; ++i) nz |= s[i];
     if (nz == 0u) continue;
-    count_column<P, Heal>(f, a.n, s, static_cast<uint32_t>(col), a.reports + stripe * a.report_stride, a.rows, at);
+    count_column<P, Heal>(f, a.n, s, static_cast<uint32_t>(t.col), a.reports + t.stripe * a.report_stride, a.rows,
+                          t.at);
   }
 }
 
@@ -242,27 +159,20 @@ hipError_t launch_scrub_init(uint32_t* reports, uint64_t report_stride, int n, u
   return hipGetLastError();
 }
 
-#define HRS_SCRUB_DISPATCH(fn, heal)         \
-  switch (a.p) {                             \
-    case 1: return fn<1, heal>(a, s);        \
-    case 2: return fn<2, heal>(a, s);        \
-    case 3: return fn<3, heal>(a, s);        \
-    case 4: return fn<4, heal>(a, s);        \
-    case 5: return fn<5, heal>(a, s);        \
-    case 6: return fn<6, heal>(a, s);        \
-    case 7: return fn<7, heal>(a, s);        \
-    case 8: return fn<8, heal>(a, s);        \
-    default: return hipErrorInvalidValue;    \
-  }
+hipError_t launch_scrub(const ScrubArgs& a, hipStream_t s) {
+  return dispatch_p<1, 8>(a.p, [&](auto P) { return launch_windows<P, false>(a, s); });
+}
 
-hipError_t launch_scrub(const ScrubArgs& a, hipStream_t s) { HRS_SCRUB_DISPATCH(launch_windows, false) }
+hipError_t launch_scrub_bytewise(const ScrubArgs& a, hipStream_t s) {
+  return dispatch_p<1, 8>(a.p, [&](auto P) { return launch_columns<P, false>(a, s); });
+}
 
-hipError_t launch_scrub_bytewise(const ScrubArgs& a, hipStream_t s) { HRS_SCRUB_DISPATCH(launch_columns, false) }
+hipError_t launch_heal(const ScrubArgs& a, hipStream_t s) {
+  return dispatch_p<1, 8>(a.p, [&](auto P) { return launch_windows<P, true>(a, s); });
+}
 
-hipError_t launch_heal(const ScrubArgs& a, hipStream_t s) { HRS_SCRUB_DISPATCH(launch_windows, true) }
-
-hipError_t launch_heal_bytewise(const ScrubArgs& a, hipStream_t s) { HRS_SCRUB_DISPATCH(launch_columns, true) }
-
-#undef HRS_SCRUB_DISPATCH
+hipError_t launch_heal_bytewise(const ScrubArgs& a, hipStream_t s) {
+  return dispatch_p<1, 8>(a.p, [&](auto P) { return launch_columns<P, true>(a, s); });
+}
 
 }  // namespace hrs

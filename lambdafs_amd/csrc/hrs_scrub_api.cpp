@@ -1,12 +1,22 @@
 // Stripe scrubbing and healing behind the C ABI: the scalar
 // computeErrorLocations on the host (hrs_compute_error_locations, host-only
 // handles included), the device-resident batches (hrs_scrub_dev, hrs_heal_dev,
-// and hrs_scrub_crc_dev, hrs_heal_crc_dev with the cells' CRC-32s from the same
-// pass) and one stripe healed on the CPU (hrs_heal_host). The host-memory batches are
-// in hrs_batch_api.cpp beside the pipeline they share. The per-column algorithm
-// is hrs_locator.hpp, the same code the kernels of hrs_scrub.hip run.
+// hrs_scrub_crc_dev, hrs_heal_crc_dev with the cells' CRC-32s from the same
+// pass, and hrs_heal_erased_dev with its erasure patterns: validated,
+// de-duplicated, with the constants the kernels of hrs_heal_erased.hip
+// multiply by) and one stripe healed on the CPU (hrs_heal_host,
+// hrs_heal_erased_host), the kernels' byte-exact reference. The host-memory
+// batches are in hrs_batch_api.cpp beside the pipeline they share. The
+// per-column algorithm is hrs_locator.hpp, the same code the kernels run.
+//
+// The entry points share one argument gate (scrub_args_ok), the device calls
+// one window / tail launcher (run_windows_tail) and the CPU calls one column
+// loop (heal_stripe).
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
+#include <cstring>
+#include <map>
 #include <string>
 #include <vector>
 
@@ -14,7 +24,9 @@
 #include "gf256.hpp"
 #include "hrs_codec.hpp"
 #include "hrs_crc.hpp"
+#include "hrs_heal_erased.hpp"
 #include "hrs_internal.hpp"
+#include "hrs_launch.hpp"
 #include "hrs_locator.hpp"
 
 namespace hrs::api {
@@ -22,11 +34,12 @@ namespace hrs::api {
 namespace {
 
 constexpr hrs::gf::Tables kHostTables = hrs::gf::make_tables();
+constexpr hrs::locator::Field kHostField{kHostTables.exp, kHostTables.log};
 
 template <int P>
-void column_syndromes(const hrs::locator::Field& f, int n, const int* data, uint8_t* out) {
+void column_syndromes(int n, const int* data, uint8_t* out) {
   uint8_t s[P] = {};
-  for (int l = n - 1; l >= 0; --l) hrs::locator::horner_step<P>(f, s, static_cast<uint8_t>(data[l]));
+  for (int l = n - 1; l >= 0; --l) hrs::locator::horner_step<P>(kHostField, s, static_cast<uint8_t>(data[l]));
   for (int i = 0; i < P; ++i) out[i] = s[i];
 }
 
@@ -44,11 +57,54 @@ hrs_status scrub_code_ok(hrs_codec* c, size_t report_stride, bool with_reports) 
   return HRS_OK;
 }
 
-hrs_status run_scrub(hrs_codec* c, const uint8_t* const* rows, size_t stride, size_t len, size_t nstripes,
-                     uint32_t* reports, size_t report_stride, hipStream_t s, bool heal) {
+// A patch through one of two equal row pointers would change the other's column.
+hrs_status heal_rows_ok(hrs_codec* c, const uint8_t* const* rows) {
+  for (int l = 0; l < c->n; ++l)
+    if (!rows[l]) return fail(c, HRS_EINVAL, "row %d is NULL", l);
+  for (int l = 1; l < c->n; ++l)
+    for (int m = 0; m < l; ++m)
+      if (rows[l] == rows[m]) return fail(c, HRS_EINVAL, "rows %d and %d are one pointer: healing writes the rows", m, l);
+  return HRS_OK;
+}
+
+hrs_status scrub_args_ok(hrs_codec* c, const void* cells, const uint32_t* reports, size_t report_stride, size_t len,
+                         size_t nstripes, unsigned flags, const char* erased_what, int erased_count,
+                         const int* erased) {
+  if (!c) return HRS_EINVAL;
+  const bool with_reports = flags & kScrubWithReports, image = flags & kScrubImage;
+  hrs_status st = scrub_code_ok(c, report_stride, with_reports);
+  if (st != HRS_OK) return st;
+  if (!cells || !reports)
+    return fail(c, HRS_EINVAL, "%s or %s is NULL", image ? "stripes" : "rows", with_reports ? "reports" : "report");
+  if (!image) {
+    const uint8_t* const* rows = static_cast<const uint8_t* const*>(cells);
+    if (flags & kScrubRowsWritten) {
+      st = heal_rows_ok(c, rows);
+      if (st != HRS_OK) return st;
+    } else {
+      for (int l = 0; l < c->n; ++l)
+        if (!rows[l]) return fail(c, HRS_EINVAL, "row %d is NULL", l);
+    }
+  }
+  if (erased_what && (erased_count < 0 || (erased_count > 0 && !erased)))
+    return fail(c, HRS_EINVAL, "%s %d with %s erased list", erased_what, erased_count, erased ? "an" : "no");
+  if (nstripes > 0x7fffffffu) return fail(c, HRS_EINVAL, "too many stripes");
+  if (len > 0xffffffffu) return fail(c, HRS_EINVAL, "rows of %zu bytes: column indices are 32-bit", len);
+  return HRS_OK;
+}
+
+namespace {
+
+// Empty reports, then `windows` over the whole 2 KiB windows (rows and stride
+// 16-byte aligned, not kernel mode 2) and `tail` over the columns from col0
+// on, both reading the ScrubArgs `a` this fills. `what` names the call in
+// launch errors. The handle's last kernel is the window kernel when one ran.
+template <class Windows, class Tail>
+hrs_status run_windows_tail(hrs_codec* c, hrs::ScrubArgs& a, const uint8_t* const* rows, size_t stride, size_t len,
+                            size_t nstripes, uint32_t* reports, size_t report_stride, hipStream_t s,
+                            const std::string& what, Windows windows, Tail tail) {
   hipError_t e = hrs::launch_scrub_init(reports, report_stride, c->n, nstripes, s);
   if (e != hipSuccess) return hip_fail(c, e, "scrub init launch");
-  hrs::ScrubArgs a{};
   bool vec_ok = stride % 16 == 0 && c->kernel_mode != 2;
   for (int l = 0; l < c->n; ++l) {
     a.rows[l] = rows[l];
@@ -63,60 +119,80 @@ hrs_status run_scrub(hrs_codec* c, const uint8_t* const* rows, size_t stride, si
   a.nwin = vec_ok ? len / hrs::kWindowBytes : 0;
   if (a.nwin > 0) {
     a.ntasks = a.nwin * nstripes;
-    e = heal ? hrs::launch_heal(a, s) : hrs::launch_scrub(a, s);
-    if (e != hipSuccess) return hip_fail(c, e, heal ? "heal launch" : "scrub launch");
+    if ((e = windows()) != hipSuccess) return hip_fail(c, e, (what + " launch").c_str());
     c->last_kernel = hrs::last_kernel();
   }
   a.col0 = a.nwin * hrs::kWindowBytes;
   if (a.col0 < len) {
     a.ntasks = (len - a.col0) * nstripes;
-    e = heal ? hrs::launch_heal_bytewise(a, s) : hrs::launch_scrub_bytewise(a, s);
-    if (e != hipSuccess) return hip_fail(c, e, heal ? "heal bytewise launch" : "scrub bytewise launch");
+    if ((e = tail()) != hipSuccess) return hip_fail(c, e, (what + " bytewise launch").c_str());
     if (a.nwin == 0) c->last_kernel = hrs::last_kernel();
   }
   return HRS_OK;
 }
 
+}  // namespace
+
+hrs_status run_scrub(hrs_codec* c, const uint8_t* const* rows, size_t stride, size_t len, size_t nstripes,
+                     uint32_t* reports, size_t report_stride, hipStream_t s, bool heal) {
+  hrs::ScrubArgs a{};
+  return run_windows_tail(
+      c, a, rows, stride, len, nstripes, reports, report_stride, s, heal ? "heal" : "scrub",
+      [&] { return heal ? hrs::launch_heal(a, s) : hrs::launch_scrub(a, s); },
+      [&] { return heal ? hrs::launch_heal_bytewise(a, s) : hrs::launch_scrub_bytewise(a, s); });
+}
+
 namespace {
 
-// One stripe on the CPU: the column loop of hrs_heal_host.
+// One stripe on the CPU: the column loop of hrs_heal_host (an empty pattern,
+// locate() on the column's syndromes) and hrs_heal_erased_host (the erased
+// cells count as zero and are rebuilt, locate_errata()).
 template <int P>
-void heal_stripe(const hrs::locator::Field& f, int n, uint8_t* const* rows, size_t len, uint32_t* rep) {
+void heal_stripe(int n, uint8_t* const* rows, size_t len, const hrs::ErasePattern& pt, uint32_t* rep) {
+  const hrs::locator::Field& f = kHostField;
+  const int e = pt.e;
   for (size_t col = 0; col < len; ++col) {
     uint8_t s[P] = {};
-    for (int l = n - 1; l >= 0; --l) hrs::locator::horner_step<P>(f, s, rows[l][col]);
-    uint32_t nz = 0;
-    for (int i = 0; i < P; ++i) nz |= s[i];
-    if (nz == 0) continue;
-    int nloc = 0;
-    uint8_t loc[hrs::locator::kMaxErrors], err[hrs::locator::kMaxErrors];
-    const bool resolved = hrs::locator::locate(f, n, P, s, &nloc, loc, err);
+    for (int l = n - 1; l >= 0; --l) {
+      const bool gone = (pt.mask[l >> 5] >> (l & 31)) & 1u;
+      hrs::locator::horner_step<P>(f, s, gone ? uint8_t{0} : rows[l][col]);
+    }
+    int nloc = 0, state;
+    uint8_t loc[hrs::locator::kMaxErrors], u[hrs::locator::kMaxErrors], v[hrs::locator::kMaxErased];
+    if (e == 0) {
+      uint32_t nz = 0;
+      for (int i = 0; i < P; ++i) nz |= s[i];
+      if (nz == 0) continue;
+      state = hrs::locator::locate(f, n, P, s, &nloc, loc, u) ? hrs::locator::kResolved : hrs::locator::kUnresolved;
+    } else {
+      state = hrs::locator::locate_errata<P>(f, n, s, e, pt.loc, pt.gamma, &nloc, loc, u, v);
+      for (int m = 0; m < e; ++m) rows[pt.loc[m]][col] = v[m];
+      if (state == hrs::locator::kConsistent) continue;
+    }
     ++rep[HRS_SCRUB_BAD];
     if (rep[HRS_SCRUB_FIRST_BAD] == HRS_SCRUB_NONE) rep[HRS_SCRUB_FIRST_BAD] = static_cast<uint32_t>(col);
-    if (!resolved) {  // left as it is, even where the Java wrote into it before returning false
+    if (state == hrs::locator::kUnresolved) {  // left as it is, even where the Java wrote into it before returning false
       ++rep[HRS_SCRUB_UNRESOLVED];
       continue;
     }
     for (int j = 0; j < nloc; ++j) {
       ++rep[HRS_SCRUB_HEAD + loc[j]];
-      if (err[j] == 0) continue;  // a blamed location whose value stands: nothing to store
-      rows[loc[j]][col] ^= err[j];
+      if (u[j] == 0) continue;  // a blamed location whose value stands: nothing to store
+      rows[loc[j]][col] ^= u[j];
       ++rep[HRS_SCRUB_PATCHED];
     }
   }
 }
 
-}  // namespace
-
-// A patch through one of two equal row pointers would change the other's column.
-hrs_status heal_rows_ok(hrs_codec* c, const uint8_t* const* rows) {
-  for (int l = 0; l < c->n; ++l)
-    if (!rows[l]) return fail(c, HRS_EINVAL, "row %d is NULL", l);
-  for (int l = 1; l < c->n; ++l)
-    for (int m = 0; m < l; ++m)
-      if (rows[l] == rows[m]) return fail(c, HRS_EINVAL, "rows %d and %d are one pointer: healing writes the rows", m, l);
+// hrs_heal_host and hrs_heal_erased_host after their argument checks.
+hrs_status heal_host(hrs_codec* c, uint8_t* const* rows, size_t len, const hrs::ErasePattern& pt, uint32_t* report) {
+  if (len == 0) return HRS_OK;
+  for (int e = 0; e < HRS_SCRUB_HEAD + c->n; ++e) report[e] = e == HRS_SCRUB_FIRST_BAD ? HRS_SCRUB_NONE : 0u;
+  (void)hrs::dispatch_p<1, 8>(c->p, [&](auto P) { heal_stripe<P>(c->n, rows, len, pt, report); });
   return HRS_OK;
 }
+
+}  // namespace
 
 // The shapes of the one-pass kernel (hrs_scrub_crc.hip). Device-resident jobs
 // take it too: measured 13 % faster than scrub + hrs_crc32_dev.
@@ -183,24 +259,24 @@ hrs_status run_scrub_crc(hrs_codec* c, const uint8_t* const* rows, size_t stride
 
 namespace {
 
+// hrs_scrub_dev and hrs_heal_dev.
+hrs_status scrub_dev_entry(hrs_codec* c, const uint8_t* const* rows, size_t stride, size_t len, size_t nstripes,
+                           uint32_t* reports, size_t report_stride, void* stream, bool heal) {
+  const hrs_status st = scrub_args_ok(c, rows, reports, report_stride, len, nstripes,
+                                      kScrubWithReports | (heal ? kScrubRowsWritten : 0u));
+  if (st != HRS_OK || len == 0 || nstripes == 0) return st;
+  DeviceGuard g(c->device);
+  if (!g.ok) return fail(c, HRS_EDEVICE, "cannot select HIP device %d", c->device);
+  return run_scrub(c, rows, stride, len, nstripes, reports, report_stride, static_cast<hipStream_t>(stream), heal);
+}
+
 // hrs_scrub_crc_dev and hrs_heal_crc_dev: the sibling call's argument rules, then the CRC arrays'.
 hrs_status scrub_crc_dev_entry(hrs_codec* c, const uint8_t* const* rows, size_t stride, size_t len, size_t nstripes,
                                uint32_t* reports, size_t report_stride, const uint32_t* crc_in, uint32_t* crc_out,
                                void* stream, bool heal) {
-  if (!c) return HRS_EINVAL;
-  hrs_status st = scrub_code_ok(c, report_stride, true);
-  if (st != HRS_OK) return st;
-  if (!rows || !reports) return fail(c, HRS_EINVAL, "rows or reports is NULL");
-  if (heal) {
-    st = heal_rows_ok(c, rows);
-    if (st != HRS_OK) return st;
-  } else {
-    for (int l = 0; l < c->n; ++l)
-      if (!rows[l]) return fail(c, HRS_EINVAL, "row %d is NULL", l);
-  }
-  if (nstripes > 0x7fffffffu) return fail(c, HRS_EINVAL, "too many stripes");
-  if (len > 0xffffffffu) return fail(c, HRS_EINVAL, "rows of %zu bytes: column indices are 32-bit", len);
-  if (len == 0 || nstripes == 0) return HRS_OK;
+  const hrs_status st = scrub_args_ok(c, rows, reports, report_stride, len, nstripes,
+                                      kScrubWithReports | (heal ? kScrubRowsWritten : 0u));
+  if (st != HRS_OK || len == 0 || nstripes == 0) return st;
   if (!crc_out) return fail(c, HRS_EINVAL, "crc_out is NULL");
   if (!crc_arrays_apart(crc_in, crc_out, nstripes * static_cast<size_t>(c->n)))
     return fail(c, HRS_EINVAL, "crc_in and crc_out overlap (crc_out may only be crc_in itself)");
@@ -208,6 +284,78 @@ hrs_status scrub_crc_dev_entry(hrs_codec* c, const uint8_t* const* rows, size_t 
   if (!g.ok) return fail(c, HRS_EDEVICE, "cannot select HIP device %d", c->device);
   return run_scrub_crc(c, rows, stride, len, nstripes, reports, report_stride, crc_in, crc_out,
                        static_cast<hipStream_t>(stream), heal);
+}
+
+// ---- heal with known erasures
+
+// The erased set of one stripe: entries up to the first negative one (or
+// `cap`), sorted ascending into `key`. HRS_EINVAL for a location outside
+// [0, n) or a repeated one, HRS_ETOOMANY for more than p of them.
+hrs_status erased_key(hrs_codec* c, const int* erased, int cap, size_t stripe, std::vector<int>& key) {
+  key.clear();
+  for (int t = 0; t < cap && erased[t] >= 0; ++t) {
+    if (erased[t] >= c->n)
+      return fail(c, HRS_EINVAL, "stripe %zu: erased location %d is outside [0, %d)", stripe, erased[t], c->n);
+    key.push_back(erased[t]);
+  }
+  std::sort(key.begin(), key.end());
+  for (size_t t = 1; t < key.size(); ++t)
+    if (key[t] == key[t - 1]) return fail(c, HRS_EINVAL, "stripe %zu: erased location %d is listed twice", stripe, key[t]);
+  if (static_cast<int>(key.size()) > c->p)
+    return fail(c, HRS_ETOOMANY, "stripe %zu: %zu erased locations, the code repairs %d", stripe, key.size(), c->p);
+  return HRS_OK;
+}
+
+// The device table entry of an erased set (hrs_heal_erased.hpp).
+hrs::ErasePattern make_pattern(int p, const std::vector<int>& key) {
+  const hrs::locator::Field& f = kHostField;
+  hrs::ErasePattern pt{};
+  const int e = static_cast<int>(key.size()), pp = p - e;
+  pt.e = e;
+  for (int m = 0; m < e; ++m) {
+    pt.loc[m] = static_cast<uint8_t>(key[m]);
+    pt.mask[key[m] >> 5] |= 1u << (key[m] & 31);
+  }
+  while ((pt.mask[pt.spare >> 5] >> (pt.spare & 31)) & 1u) ++pt.spare;
+  hrs::locator::erasure_locator(f, e, pt.loc, pt.gamma);
+  uint8_t mat[hrs::locator::kMaxSyndromes][hrs::locator::kMaxSyndromes] = {};
+  for (int o = 0; o < pp; ++o)
+    for (int j = 0; j <= e; ++j) mat[o][o + e - j] = pt.gamma[j];
+  if (e > 0) {
+    std::vector<uint8_t> v(static_cast<size_t>(e) * e);  // v[i][m] = alpha^(loc[m] i)
+    for (int i = 0; i < e; ++i)
+      for (int m = 0; m < e; ++m) v[static_cast<size_t>(i) * e + m] = hrs::gf::alpha_pow(static_cast<long>(key[m]) * i);
+    gf_invert(v, e);  // distinct locations: never singular
+    for (int m = 0; m < e; ++m)
+      for (int i = 0; i < e; ++i) mat[pp + m][i] = v[static_cast<size_t>(m) * e + i];
+  }
+  for (int i = 0; i < p; ++i)
+    for (int o = 0; o < p; ++o) pt.cw[i] |= static_cast<uint64_t>(mat[o][i]) << (8 * o);
+  return pt;
+}
+
+hrs_status run_heal_erased(hrs_codec* c, uint8_t* const* rows, size_t stride, size_t len, size_t nstripes,
+                           const std::vector<hrs::ErasePattern>& pats, const std::vector<int32_t>& pat,
+                           uint32_t* reports, size_t report_stride, hipStream_t s) {
+  const size_t pat_bytes = pats.size() * sizeof(hrs::ErasePattern);
+  const size_t need = pat_bytes + pat.size() * sizeof(int32_t);
+  hrs_codec::BatchSlot* sl = nullptr;
+  hrs_status st = batch_slot_acquire(c, need, &sl);
+  if (st != HRS_OK) return st;
+  std::memcpy(sl->host, pats.data(), pat_bytes);
+  std::memcpy(sl->host + pat_bytes, pat.data(), pat.size() * sizeof(int32_t));
+  const hipError_t e = hipMemcpyAsync(sl->dev, sl->host, need, hipMemcpyHostToDevice, s);
+  if (e != hipSuccess) return hip_fail(c, e, "hipMemcpyAsync patterns");
+  hrs::HealErasedArgs a{};
+  a.pats = reinterpret_cast<const hrs::ErasePattern*>(sl->dev);
+  a.pat = reinterpret_cast<const int32_t*>(sl->dev + pat_bytes);
+  st = run_windows_tail(
+      c, a.s, rows, stride, len, nstripes, reports, report_stride, s, "heal erased",
+      [&] { return hrs::launch_heal_erased(a, s); }, [&] { return hrs::launch_heal_erased_bytewise(a, s); });
+  // the slot's table may be in use whether or not every launch went out
+  if (hipEventRecord(sl->done, s) == hipSuccess) sl->pending = true;
+  else (void)hipStreamSynchronize(s);
+  return st;
 }
 
 }  // namespace
@@ -228,18 +376,8 @@ hrs_status hrs_compute_error_locations(const hrs_codec* cc, int* data, int* loca
   if (st != HRS_OK) return st;
   for (int l = 0; l < c->n; ++l)
     if (data[l] < 0 || data[l] > 255) return fail(c, HRS_EINVAL, "data[%d] = %d is outside [0, 255]", l, data[l]);
-  const hrs::locator::Field f{kHostTables.exp, kHostTables.log};
   uint8_t s[hrs::locator::kMaxSyndromes] = {};
-  switch (c->p) {
-    case 1: column_syndromes<1>(f, c->n, data, s); break;
-    case 2: column_syndromes<2>(f, c->n, data, s); break;
-    case 3: column_syndromes<3>(f, c->n, data, s); break;
-    case 4: column_syndromes<4>(f, c->n, data, s); break;
-    case 5: column_syndromes<5>(f, c->n, data, s); break;
-    case 6: column_syndromes<6>(f, c->n, data, s); break;
-    case 7: column_syndromes<7>(f, c->n, data, s); break;
-    default: column_syndromes<8>(f, c->n, data, s); break;
-  }
+  (void)hrs::dispatch_p<1, 8>(c->p, [&](auto P) { column_syndromes<P>(c->n, data, s); });
   *num_locations = 0;
   bool clean = true;
   for (int i = 0; i < c->p; ++i) clean &= s[i] == 0;
@@ -249,7 +387,7 @@ hrs_status hrs_compute_error_locations(const hrs_codec* cc, int* data, int* loca
   }
   int nloc = 0;
   uint8_t loc[hrs::locator::kMaxErrors], err[hrs::locator::kMaxErrors];
-  *resolved = hrs::locator::locate(f, c->n, c->p, s, &nloc, loc, err) ? 1 : 0;
+  *resolved = hrs::locator::locate(kHostField, c->n, c->p, s, &nloc, loc, err) ? 1 : 0;
   for (int j = 0; j < nloc; ++j) {  // ReedSolomonCode.java:281-285: the decoded values are written back
     locations[j] = loc[j];
     data[loc[j]] ^= err[j];
@@ -260,34 +398,12 @@ hrs_status hrs_compute_error_locations(const hrs_codec* cc, int* data, int* loca
 
 hrs_status hrs_scrub_dev(hrs_codec* c, const uint8_t* const* rows, size_t stride, size_t len, size_t nstripes,
                          uint32_t* reports, size_t report_stride, void* stream) {
-  if (!c) return HRS_EINVAL;
-  hrs_status st = scrub_code_ok(c, report_stride, true);
-  if (st != HRS_OK) return st;
-  if (!rows || !reports) return fail(c, HRS_EINVAL, "rows or reports is NULL");
-  for (int l = 0; l < c->n; ++l)
-    if (!rows[l]) return fail(c, HRS_EINVAL, "row %d is NULL", l);
-  if (nstripes > 0x7fffffffu) return fail(c, HRS_EINVAL, "too many stripes");
-  if (len > 0xffffffffu) return fail(c, HRS_EINVAL, "rows of %zu bytes: column indices are 32-bit", len);
-  if (len == 0 || nstripes == 0) return HRS_OK;
-  DeviceGuard g(c->device);
-  if (!g.ok) return fail(c, HRS_EDEVICE, "cannot select HIP device %d", c->device);
-  return run_scrub(c, rows, stride, len, nstripes, reports, report_stride, static_cast<hipStream_t>(stream), false);
+  return scrub_dev_entry(c, rows, stride, len, nstripes, reports, report_stride, stream, false);
 }
 
 hrs_status hrs_heal_dev(hrs_codec* c, uint8_t* const* rows, size_t stride, size_t len, size_t nstripes,
                         uint32_t* reports, size_t report_stride, void* stream) {
-  if (!c) return HRS_EINVAL;
-  hrs_status st = scrub_code_ok(c, report_stride, true);
-  if (st != HRS_OK) return st;
-  if (!rows || !reports) return fail(c, HRS_EINVAL, "rows or reports is NULL");
-  st = heal_rows_ok(c, rows);
-  if (st != HRS_OK) return st;
-  if (nstripes > 0x7fffffffu) return fail(c, HRS_EINVAL, "too many stripes");
-  if (len > 0xffffffffu) return fail(c, HRS_EINVAL, "rows of %zu bytes: column indices are 32-bit", len);
-  if (len == 0 || nstripes == 0) return HRS_OK;
-  DeviceGuard g(c->device);
-  if (!g.ok) return fail(c, HRS_EDEVICE, "cannot select HIP device %d", c->device);
-  return run_scrub(c, rows, stride, len, nstripes, reports, report_stride, static_cast<hipStream_t>(stream), true);
+  return scrub_dev_entry(c, rows, stride, len, nstripes, reports, report_stride, stream, true);
 }
 
 hrs_status hrs_scrub_crc_dev(hrs_codec* c, const uint8_t* const* rows, size_t stride, size_t len, size_t nstripes,
@@ -304,27 +420,51 @@ hrs_status hrs_heal_crc_dev(hrs_codec* c, uint8_t* const* rows, size_t stride, s
 
 hrs_status hrs_heal_host(const hrs_codec* cc, uint8_t* const* rows, size_t len, uint32_t* report) {
   auto* c = const_cast<hrs_codec*>(cc);
-  if (!c) return HRS_EINVAL;
-  hrs_status st = scrub_code_ok(c, 0, false);
+  const hrs_status st = scrub_args_ok(c, rows, report, 0, len, 1, kScrubRowsWritten);
   if (st != HRS_OK) return st;
-  if (!rows || !report) return fail(c, HRS_EINVAL, "rows or report is NULL");
-  st = heal_rows_ok(c, rows);
+  return heal_host(c, rows, len, hrs::ErasePattern{}, report);
+}
+
+hrs_status hrs_heal_erased_dev(hrs_codec* c, uint8_t* const* rows, size_t stride, size_t len, size_t nstripes,
+                               const int* erased, int max_erased, uint32_t* reports, size_t report_stride,
+                               void* stream) {
+  hrs_status st = scrub_args_ok(c, rows, reports, report_stride, len, nstripes, kScrubWithReports | kScrubRowsWritten,
+                                "max_erased", max_erased, erased);
   if (st != HRS_OK) return st;
-  if (len > 0xffffffffu) return fail(c, HRS_EINVAL, "rows of %zu bytes: column indices are 32-bit", len);
-  if (len == 0) return HRS_OK;
-  for (int e = 0; e < HRS_SCRUB_HEAD + c->n; ++e) report[e] = e == HRS_SCRUB_FIRST_BAD ? HRS_SCRUB_NONE : 0u;
-  const hrs::locator::Field f{kHostTables.exp, kHostTables.log};
-  switch (c->p) {
-    case 1: heal_stripe<1>(f, c->n, rows, len, report); break;
-    case 2: heal_stripe<2>(f, c->n, rows, len, report); break;
-    case 3: heal_stripe<3>(f, c->n, rows, len, report); break;
-    case 4: heal_stripe<4>(f, c->n, rows, len, report); break;
-    case 5: heal_stripe<5>(f, c->n, rows, len, report); break;
-    case 6: heal_stripe<6>(f, c->n, rows, len, report); break;
-    case 7: heal_stripe<7>(f, c->n, rows, len, report); break;
-    default: heal_stripe<8>(f, c->n, rows, len, report); break;
+  std::vector<hrs::ErasePattern> pats;
+  std::vector<int32_t> pat(max_erased > 0 ? nstripes : 0, 0);
+  if (max_erased > 0) {
+    std::map<std::vector<int>, int32_t> ids;
+    std::vector<int> key;
+    for (size_t s = 0; s < nstripes; ++s) {
+      st = erased_key(c, erased + s * static_cast<size_t>(max_erased), max_erased, s, key);
+      if (st != HRS_OK) return st;
+      auto it = ids.find(key);
+      if (it == ids.end()) {
+        it = ids.emplace(key, static_cast<int32_t>(pats.size())).first;
+        pats.push_back(make_pattern(c->p, key));
+      }
+      pat[s] = it->second;
+    }
   }
-  return HRS_OK;
+  if (len == 0 || nstripes == 0) return HRS_OK;
+  DeviceGuard g(c->device);
+  if (!g.ok) return fail(c, HRS_EDEVICE, "cannot select HIP device %d", c->device);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (max_erased == 0)  // nothing can be erased: the heal itself
+    return run_scrub(c, rows, stride, len, nstripes, reports, report_stride, s, true);
+  return run_heal_erased(c, rows, stride, len, nstripes, pats, pat, reports, report_stride, s);
+}
+
+hrs_status hrs_heal_erased_host(const hrs_codec* cc, uint8_t* const* rows, size_t len, const int* erased,
+                                int num_erased, uint32_t* report) {
+  auto* c = const_cast<hrs_codec*>(cc);
+  hrs_status st = scrub_args_ok(c, rows, report, 0, len, 1, kScrubRowsWritten, "num_erased", num_erased, erased);
+  if (st != HRS_OK) return st;
+  std::vector<int> key;
+  st = erased_key(c, erased, num_erased, 0, key);
+  if (st != HRS_OK) return st;
+  return heal_host(c, rows, len, make_pattern(c->p, key), report);
 }
 
 }  // extern "C"

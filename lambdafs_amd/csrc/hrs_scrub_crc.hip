@@ -9,7 +9,9 @@
 //
 // The walk is scrub_kernel's (hrs_scrub.hip): one wave per (stripe, 2 KiB
 // window), rows from location n - 1 down to 0 in groups, Horner in the
-// bit-sliced domain, one ballot for the clean window. Before a row is sliced
+// bit-sliced domain, one ballot for the clean window; the Horner step, the
+// dirty window's column walk, count_column and the per-wave histogram are the
+// same code, hrs_scrub_device.hpp. Before a row is sliced
 // its eight words feed the lane's two piece CRCs (slicing-by-4, the chains of
 // a group in lockstep), which are joined with Z_1024 and the Z_{16*2^t} lane
 // tree exactly as decode_crc_kernel joins an output's: lane 0 writes the raw
@@ -40,11 +42,10 @@
 #include "hrs_device.hpp"
 #include "hrs_launch.hpp"
 #include "hrs_locator.hpp"
+#include "hrs_scrub_device.hpp"
 
 namespace hrs {
 namespace {
-
-__constant__ gf::Tables d_scrub_crc_tables = gf::make_tables();
 
 constexpr int kHistWords = kScrubHead + kScrubCrcMaxRows;  // per wave
 constexpr int kFieldWords = (512 + 256) / 4;               // exp + log after the CRC image
@@ -53,38 +54,6 @@ constexpr size_t scrub_crc_lds_bytes(int threads) {
   return (static_cast<size_t>(kCrcLdsWordsA) + kFieldWords + static_cast<size_t>(threads / 64) * kHistWords) * 4;
 }
 static_assert(scrub_crc_lds_bytes(1024) <= 163840, "the CRC image, the field tables and 16 histograms fit one CU's LDS");
-
-// count_column of hrs_scrub.hip over this kernel's 16-row arguments: one bad
-// column into the wave's histogram h; Heal also writes the resolved column
-// back and counts the bytes stored in word 3.
-template <int P, bool Heal>
-__device__ __forceinline__ void count_column(const locator::Field& f, int n, const uint8_t (&s)[P], uint32_t col,
-                                             uint32_t* h, const uint8_t* const* rows, uint64_t at) {
-  int nloc = 0;
-  uint8_t loc[locator::kMaxErrors], err[locator::kMaxErrors];
-  const bool resolved = locator::locate(f, n, P, s, &nloc, loc, err);
-  atomicAdd(&h[0], 1u);
-  atomicMin(&h[2], col);
-  if (!resolved) {
-    atomicAdd(&h[1], 1u);
-  } else {
-    // at most P / 2 errors resolve; constant indices keep loc / err in registers
-#pragma unroll
-    for (int j = 0; j < P / 2; ++j)
-      if (j < nloc) atomicAdd(&h[kScrubHead + loc[j]], 1u);
-    if constexpr (Heal) {
-      uint32_t patched = 0u;
-#pragma unroll
-      for (int j = 0; j < P / 2; ++j)
-        if (j < nloc && err[j] != 0) {
-          uint8_t* q = const_cast<uint8_t*>(rows[loc[j]]) + at;
-          *q = static_cast<uint8_t>(*q ^ err[j]);
-          ++patched;
-        }
-      if (patched != 0u) atomicAdd(&h[kScrubPatched], patched);
-    }
-  }
-}
 
 // Rows top - 1 .. top - R of the window at `base`: loaded together, their 2R
 // piece chains, R Z_1024 joins and R lane trees advanced in lockstep (8R
@@ -138,13 +107,7 @@ __device__ __forceinline__ void rows_group(const ScrubCrcArgs& a, int top, uint6
 #pragma unroll
   for (int g = 0; g < R; ++g) {
     bitslice(w[g]);
-#pragma unroll
-    for (int i = 0; i < P; ++i) {
-#pragma unroll
-      for (int r = 0; r < i; ++r) xtime(acc[i]);
-#pragma unroll
-      for (int q = 0; q < 8; ++q) acc[i][q] ^= w[g][q];
-    }
+    horner_sliced<P>(acc, w[g]);
   }
 }
 
@@ -158,10 +121,8 @@ __global__ void __launch_bounds__(THREADS) scrub_crc_kernel(const ScrubCrcArgs a
   uint8_t* s_exp = reinterpret_cast<uint8_t*>(lds + kCrcLdsWordsA);
   uint8_t* s_log = s_exp + 512;
   uint32_t* s_hist = lds + kCrcLdsWordsA + kFieldWords;
-  for (int i = threadIdx.x; i < 512; i += THREADS) s_exp[i] = d_scrub_crc_tables.exp[i];
-  for (int i = threadIdx.x; i < 256; i += THREADS) s_log[i] = d_scrub_crc_tables.log[i];
-  for (int i = threadIdx.x; i < (THREADS / 64) * kHistWords; i += THREADS)
-    s_hist[i] = i % kHistWords == 2 ? kScrubNone : 0u;
+  load_field_tables(s_exp, s_log, THREADS);
+  hist_init(s_hist, kHistWords, THREADS / 64);
   __syncthreads();
   const locator::Field f{s_exp, s_log};
   const int lane = threadIdx.x & 63;
@@ -206,59 +167,25 @@ __global__ void __launch_bounds__(THREADS) scrub_crc_kernel(const ScrubCrcArgs a
       for (int q = 0; q < 8; ++q) any |= acc[i][q];
     if (__ballot(any != 0u) == 0ull) continue;  // clean window (wave-uniform)
 
-    // slow path, as in scrub_kernel: the lane's 32 columns are bytes 0..3 of
-    // words 0..7 of the un-sliced syndromes
+    // slow path: un-slice the syndromes and run the locator on the lane's bad columns
 #pragma unroll
     for (int i = 0; i < P; ++i) bitslice(acc[i]);
     if (any != 0u) {
-#pragma unroll 1
-      for (int x = 0; x < 8; ++x) {
-        uint32_t cur[P];
-#pragma unroll
-        for (int i = 0; i < P; ++i) {
-          uint32_t v = acc[i][0];
-#pragma unroll
-          for (int q = 1; q < 8; ++q) v = (x == q) ? acc[i][q] : v;
-          cur[i] = v;
-        }
-        uint32_t anyw = 0u;
-#pragma unroll
-        for (int i = 0; i < P; ++i) anyw |= cur[i];
-        if (anyw == 0u) continue;
-#pragma unroll 1
-        for (int b = 0; b < 4; ++b) {
-          uint8_t s[P];
-          uint32_t nz = 0u;
-#pragma unroll
-          for (int i = 0; i < P; ++i) {
-            s[i] = static_cast<uint8_t>(cur[i] >> (8 * b));
-            nz |= s[i];
-          }
-          if (nz == 0u) continue;
-          const uint32_t col = static_cast<uint32_t>(off) + (x >> 2) * 1024u + lane * 16u + (x & 3) * 4u + b;
-          count_column<P, Heal>(f, a.n, s, col, hist, a.rows, stripe * a.stride + col);
-        }
-      }
+      // count_column with constant indices: loc / err stay in registers (no scratch)
+      auto column = [&](const uint8_t(&s)[P], uint32_t col, int, int) {
+        count_column<P, Heal, true>(f, a.n, s, col, hist, a.rows, stripe * a.stride + col);
+      };
+      for_each_bad_column<P>(acc, static_cast<uint32_t>(off), lane, column);
     }
-    __builtin_amdgcn_wave_barrier();
     if constexpr (Heal) {
       // the wave stored into this window: its raw words are stale (redo kernel)
+      __builtin_amdgcn_wave_barrier();
       if (lane == 0 && hist[kScrubPatched] != 0u) {
         const unsigned long long at = atomicAdd(reinterpret_cast<unsigned long long*>(a.dirty), 1ull);
         a.dirty[1 + at] = t;
       }
-      __builtin_amdgcn_wave_barrier();
     }
-    uint32_t* rep = a.reports + stripe * a.report_stride;
-    for (int e = lane; e < nwords; e += 64) {
-      const uint32_t v = atomicExch(&hist[e], e == 2 ? kScrubNone : 0u);
-      if (e == 2) {
-        if (v != kScrubNone) atomicMin(&rep[2], v);
-      } else if (v != 0u) {
-        atomicAdd(&rep[e], v);
-      }
-    }
-    __builtin_amdgcn_wave_barrier();
+    hist_flush(hist, a.reports + stripe * a.report_stride, nwords, lane);
   }
 }
 
@@ -328,21 +255,13 @@ hipError_t launch_sc(const ScrubCrcArgs& a, int cus, hipStream_t s) {
   return hipGetLastError();
 }
 
-template <bool Heal>
-hipError_t launch_sc_p(const ScrubCrcArgs& a, int cus, hipStream_t s) {
-  switch (a.p) {
-    case 2: return launch_sc<2, Heal>(a, cus, s);
-    case 3: return launch_sc<3, Heal>(a, cus, s);
-    case 4: return launch_sc<4, Heal>(a, cus, s);
-    default: return hipErrorInvalidValue;
-  }
-}
-
 }  // namespace
 
 hipError_t launch_scrub_crc(const ScrubCrcArgs& a, bool heal, int cus, hipStream_t s) {
   if (a.n < 1 || a.n > kScrubCrcMaxRows || a.nwin == 0) return hipErrorInvalidValue;
-  return heal ? launch_sc_p<true>(a, cus, s) : launch_sc_p<false>(a, cus, s);
+  return dispatch_p<2, kScrubCrcMaxP>(a.p, [&](auto P) {
+    return heal ? launch_sc<P, true>(a, cus, s) : launch_sc<P, false>(a, cus, s);
+  });
 }
 
 hipError_t launch_scrub_crc_redo(const ScrubCrcArgs& a, int cus, hipStream_t s) {
