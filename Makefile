@@ -56,7 +56,8 @@ build/hrs_fused.o: HIPFLAGS += -mllvm -pragma-unroll-threshold=1000000
 
 build/hrs_probe.o: include/hrs_probe.h
 
-# `make scrub_resources`, `make scrub_crc_resources`, `make heal_erased_resources`:
+# `make scrub_resources`, `make scrub_crc_resources`, `make heal_erased_resources`,
+# `make heal_erased_crc_resources`:
 # the compiler's resource report of every kernel of hrs_<name>.hip (the scrub
 # family carries no scratch). Not .PHONY: a phony target takes no pattern rule.
 %_resources: lambdafs_amd/csrc/hrs_%.hip $(HDRS)
@@ -65,7 +66,8 @@ build/hrs_probe.o: include/hrs_probe.h
 	    grep -E 'Function Name|VGPRs:|SGPRs:|ScratchSize|Occupancy|LDS Size'
 
 KOBJ     := build/hrs_kernels.o build/hrs_runtime.o build/hrs_batch.o build/hrs_crc.o build/hrs_fused.o build/hrs_decode_crc.o \
-            build/hrs_batch_crc.o build/hrs_gate.o build/hrs_scrub.o build/hrs_scrub_crc.o build/hrs_heal_erased.o
+            build/hrs_batch_crc.o build/hrs_gate.o build/hrs_scrub.o build/hrs_scrub_crc.o build/hrs_heal_erased.o \
+            build/hrs_heal_erased_crc.o
 
 $(LIB): $(API_OBJ) $(KOBJ) lambdafs_amd/csrc/libhrs.map
 	$(HIPCC) $(HIPFLAGS) -shared -Wl,--version-script=lambdafs_amd/csrc/libhrs.map -o $@ $(API_OBJ) $(KOBJ) \

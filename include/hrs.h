@@ -613,7 +613,9 @@ hrs_status hrs_heal_host(const hrs_codec* codec, uint8_t* const* rows, size_t le
  * quirky elimination leaves a few such columns unresolved (DESIGN.md section
  * 10.3). Past capacity the distance limit holds as for the heal; at e = p no
  * spare is left and every error goes undetected. A caller who cannot accept
- * that compares CRCs afterwards (hrs_crc32_dev). Codes as for the scrub. */
+ * that takes the cells' CRCs from the same call (hrs_heal_erased_crc_dev,
+ * hrs_heal_erased_batch_host_crc below) and compares them with the stored
+ * checksums. Codes as for the scrub. */
 
 /* Device-resident batch. rows, stride, len, nstripes, reports, report_stride
  * and stream as for hrs_heal_dev (n DEVICE pointers, none NULL, no two equal;
@@ -698,10 +700,66 @@ hrs_status hrs_heal_batch_host_crc(hrs_codec* codec, uint8_t* stripes, size_t ro
                                    size_t len, size_t nstripes, uint32_t* reports, size_t report_stride,
                                    const uint32_t* crc_in, uint32_t* crc_out);
 
+/* ---- heal with known erasures over host batches, and with block CRC-32s ----
+ * hrs_heal_erased_dev for stripes in HOST memory, and both forms with the
+ * CRC-32 of every cell from the same call. Nothing new is defined: bytes,
+ * reports, the erased list's rules (HOST int array, read up to the first
+ * negative entry per stripe; HRS_ETOOMANY above parity_size locations with the
+ * stripe named; HRS_EINVAL for a location out of range, a repeated one or
+ * max_erased < 0) and codes (rs, parity_size <= 8) are hrs_heal_erased_dev's,
+ * and max_erased == 0 is the corresponding heal call (hrs_heal_crc_dev,
+ * hrs_heal_batch_host, hrs_heal_batch_host_crc). Argument errors, the erased
+ * list's included, come before the device is selected and before any byte is
+ * copied; valid arguments on a host-only handle are HRS_EDEVICE; len == 0 or
+ * nstripes == 0 touches nothing, the CRC arrays included.
+ *
+ * CRCs follow the rules of "scrub and heal + CRC-32": crc_out[s * n + l] is
+ * the CRC-32 of hops location l of stripe s, HOPS ORDER, continued from
+ * crc_in (NULL = fresh); crc_out may be crc_in itself, any other overlap and a
+ * NULL crc_out with work to do are HRS_EINVAL. They cover the cells as they
+ * are when the call returns: rebuilt cells, patched survivors, and unresolved
+ * columns as left. A caller compares them with the stored checksums to accept
+ * the stripe, which also covers what the distance limit lets through.
+ *
+ * rs codes with 2 <= parity_size <= 4 and n <= 16, len a multiple of 2 KiB,
+ * 16-byte aligned rows and stride have one fused kernel
+ * (hrs_last_kernel "heal_erased_crc_kernel<P>": the survivors are read once,
+ * only the 2 KiB windows with a bad column are read again). Kernel mode 3
+ * always takes it for such a shape, kernel mode 2 never; kernel mode 0 takes
+ * it where it was measured faster than two passes for the memory the stripes
+ * lie in. Everything else runs hrs_heal_erased_dev's
+ * kernels, then the CRC pass over the n rows on the same stream, with
+ * identical results and hrs_last_kernel as the sibling reports it. */
+
+/* hrs_heal_erased_dev + the CRCs. crc_in / crc_out: DEVICE uint32
+ * [nstripes * n]. Asynchronous on stream. */
+hrs_status hrs_heal_erased_crc_dev(hrs_codec* codec, uint8_t* const* rows, size_t stride, size_t len, size_t nstripes,
+                                   const int* erased, int max_erased, uint32_t* reports, size_t report_stride,
+                                   const uint32_t* crc_in, uint32_t* crc_out, void* stream);
+
+/* hrs_heal_erased_dev over a HOST batch laid out as for hrs_heal_batch_host,
+ * cell-overlap rule included; reports is a HOST array. Runtime-pinned stripes
+ * are healed in place by one launch: erased cells never cross the link
+ * inbound. Any other memory is staged through the host-batch pipeline: of a
+ * stripe only its survivor rows are copied in, and only its erased cells
+ * (fully written, never read) and the cells with a nonzero count in word
+ * 4 + l are copied back: no other byte of the caller's memory is written.
+ * hrs_last_host_path as for the sibling calls. Synchronous. */
+hrs_status hrs_heal_erased_batch_host(hrs_codec* codec, uint8_t* stripes, size_t row_stride, size_t stripe_stride,
+                                      size_t len, size_t nstripes, const int* erased, int max_erased,
+                                      uint32_t* reports, size_t report_stride);
+
+/* hrs_heal_erased_batch_host + the CRCs; crc_in / crc_out are HOST uint32
+ * [nstripes * n] (read before the first chunk, written once after the last). */
+hrs_status hrs_heal_erased_batch_host_crc(hrs_codec* codec, uint8_t* stripes, size_t row_stride, size_t stripe_stride,
+                                          size_t len, size_t nstripes, const int* erased, int max_erased,
+                                          uint32_t* reports, size_t report_stride, const uint32_t* crc_in,
+                                          uint32_t* crc_out);
+
 /* Kernel selection for tests and benchmarks: 0 = auto (default), 1 = force
  * the runtime-matrix bit-sliced kernel, 2 = force the byte-granular kernel,
- * 3 = auto, except that hrs_encode_crc_dev takes the fused kernel whenever the
- * shape allows it. */
+ * 3 = auto, except that hrs_encode_crc_dev and the heal-with-erasures + CRC
+ * calls take their fused kernel whenever the shape allows it. */
 hrs_status hrs_set_kernel_mode(hrs_codec* codec, int mode);
 
 #ifdef __cplusplus

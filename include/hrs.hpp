@@ -365,6 +365,33 @@ class HipReedSolomonCode : public HipCode {
           h_);
   }
 
+  // healErasedDev plus the CRC-32 of every cell as the call leaves it
+  // (hrs_heal_erased_crc_dev): crcOut[s * n + l] in HOPS order, continued from
+  // crcIn (nullptr: fresh); device arrays.
+  void healErasedCrcDev(const std::vector<uint8_t*>& rows, size_t stride, size_t len, size_t nstripes,
+                        const int* erased, int maxErased, uint32_t* reports, size_t reportStride,
+                        const uint32_t* crcIn, uint32_t* crcOut, void* stream = nullptr) {
+    if (static_cast<int>(rows.size()) != stripeSize() + paritySize())
+      throw std::invalid_argument("healErasedCrcDev: row count does not match the codec");
+    check(hrs_heal_erased_crc_dev(h_, rows.data(), stride, len, nstripes, erased, maxErased, reports, reportStride,
+                                  crcIn, crcOut, stream), h_);
+  }
+
+  // The same over a host batch (hrs_heal_erased_batch_host /
+  // hrs_heal_erased_batch_host_crc); reports, crcIn and crcOut are host arrays.
+  void healErasedBatchHost(uint8_t* stripes, size_t rowStride, size_t stripeStride, size_t len, size_t nstripes,
+                           const int* erased, int maxErased, uint32_t* reports, size_t reportStride) {
+    check(hrs_heal_erased_batch_host(h_, stripes, rowStride, stripeStride, len, nstripes, erased, maxErased, reports,
+                                     reportStride), h_);
+  }
+
+  void healErasedBatchHostCrc(uint8_t* stripes, size_t rowStride, size_t stripeStride, size_t len, size_t nstripes,
+                              const int* erased, int maxErased, uint32_t* reports, size_t reportStride,
+                              const uint32_t* crcIn, uint32_t* crcOut) {
+    check(hrs_heal_erased_batch_host_crc(h_, stripes, rowStride, stripeStride, len, nstripes, erased, maxErased,
+                                         reports, reportStride, crcIn, crcOut), h_);
+  }
+
   // One stripe of n host rows on the CPU (hrs_heal_erased_host; host-only
   // handles included); report holds HRS_SCRUB_HEAD + n words.
   void healErasedHost(const std::vector<uint8_t*>& rows, size_t len, const std::vector<int>& erased,

@@ -48,6 +48,7 @@ EXPORTS = (
     "hrs_decode_batch_crc_dev", "hrs_decode_batch_host_crc", "hrs_encode_batch_host_crc",
     "hrs_scrub_crc_dev", "hrs_heal_crc_dev", "hrs_scrub_batch_host_crc", "hrs_heal_batch_host_crc",
     "hrs_heal_erased_dev", "hrs_heal_erased_host",
+    "hrs_heal_erased_crc_dev", "hrs_heal_erased_batch_host", "hrs_heal_erased_batch_host_crc",
 )
 # include/hrs_probe.h, exported by libhrs_probe.so
 PROBE_EXPORTS = ("hrs_probe_stream", "hrs_probe_rows")
@@ -142,6 +143,9 @@ def lib():
         "hrs_heal_batch_host_crc": ([P, P, S, S, S, S, P, S, P, P], I),
         "hrs_heal_erased_dev": ([P, PP, S, S, S, P, I, P, S, P], I),
         "hrs_heal_erased_host": ([P, PP, S, P, I, P], I),
+        "hrs_heal_erased_crc_dev": ([P, PP, S, S, S, P, I, P, S, P, P, P], I),
+        "hrs_heal_erased_batch_host": ([P, P, S, S, S, S, P, I, P, S], I),
+        "hrs_heal_erased_batch_host_crc": ([P, P, S, S, S, S, P, I, P, S, P, P], I),
     }
     for name, (args, res) in sigs.items():
         f = getattr(L, name)

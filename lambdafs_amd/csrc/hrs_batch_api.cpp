@@ -324,6 +324,17 @@ bool runtime_pinned(const void* p, size_t len) {
   return a >= b && len <= info.sizeInBytes && a - b <= info.sizeInBytes - len;
 }
 
+// Whether a kernel reaches p across the host link (the caller's pinned
+// stripes or a slot's zero-copy staging) and not in a device image.
+bool on_host(const void* p) {
+  hipPointerAttribute_t attr{};
+  if (hipPointerGetAttributes(&attr, p) != hipSuccess) {
+    (void)hipGetLastError();
+    return false;
+  }
+  return attr.type == hipMemoryTypeHost;
+}
+
 bool zero_copy_on() {
   const char* e = getenv("HRS_ZEROCOPY");
   return !(e && e[0] == '0');
@@ -957,9 +968,18 @@ hrs_status encode_batch_host_impl(hrs_codec* c, uint8_t* stripes, size_t row_str
 // run_scrub, the CRCs through the handle's device buffer as in
 // encode_batch_host_impl. A pinned cell crosses the link once when the shape
 // takes the one-pass kernel (the heal's dirty windows twice).
+// es != NULL (hrs_heal_erased_batch_host[_crc]; heal is set): run_heal_erased
+// / run_heal_erased_crc with each chunk's slice of pattern indices, uploaded
+// with the table through a batch slot on the chunk's stream (two slots:
+// acquiring one waits for the chunk that used it two chunks earlier). A
+// stripe's erased cells are never read, so a staged chunk copies in only the
+// survivor rows (the slot image keeps stale bytes at erased rows; the kernels
+// write every byte of them) and copies back the erased cells plus the cells
+// with a nonzero count in word 4 + l.
 hrs_status scrub_batch_host_impl(hrs_codec* c, const uint8_t* stripes, size_t row_stride, size_t stripe_stride,
                                  size_t len, size_t nstripes, uint32_t* reports, size_t report_stride, bool heal,
-                                 const uint32_t* crc_in = nullptr, uint32_t* crc_out = nullptr) {
+                                 const uint32_t* crc_in = nullptr, uint32_t* crc_out = nullptr,
+                                 const ErasedSets* es = nullptr) {
   DeviceGuard g(c->device);
   if (!g.ok) return fail(c, HRS_EDEVICE, "cannot select HIP device %d", c->device);
   const int n = c->n;
@@ -974,6 +994,15 @@ hrs_status scrub_batch_host_impl(hrs_codec* c, const uint8_t* stripes, size_t ro
   // the scrub or heal of stripes [s0, s0 + ns) on hs, with their CRCs when asked
   auto scrub = [&](const uint8_t* const* r, size_t stride, size_t s0, size_t ns, uint32_t* rep,
                    hipStream_t hs) -> hrs_status {
+    if (es) {
+      uint8_t* const* w = reinterpret_cast<uint8_t* const*>(const_cast<uint8_t**>(r));
+      if (!dcrc)
+        return run_heal_erased(c, w, stride, len, ns, es->pats, es->pat.data() + s0, rep,
+                               static_cast<size_t>(hrs::kScrubHead + n), hs);
+      return run_heal_erased_crc(c, w, stride, len, ns, es->pats, es->pat.data() + s0, rep,
+                                 static_cast<size_t>(hrs::kScrubHead + n), dcrc_in ? dcrc_in + s0 * n : nullptr,
+                                 dcrc + s0 * n, hs, on_host(r[0]));
+    }
     if (!dcrc) return run_scrub(c, r, stride, len, ns, rep, static_cast<size_t>(hrs::kScrubHead + n), hs, heal);
     return run_scrub_crc(c, r, stride, len, ns, rep, static_cast<size_t>(hrs::kScrubHead + n),
                          dcrc_in ? dcrc_in + s0 * n : nullptr, dcrc + s0 * n, hs, heal);
@@ -1007,7 +1036,14 @@ hrs_status scrub_batch_host_impl(hrs_codec* c, const uint8_t* stripes, size_t ro
     }
   } else {
     const std::vector<RowRun> all_rows{{0, n}};
-    auto reads = [&](size_t) -> const std::vector<RowRun>& { return all_rows; };
+    std::vector<std::vector<RowRun>> survivor_runs(es ? es->keys.size() : 0);  // per pattern
+    for (size_t id = 0; id < survivor_runs.size(); ++id) {
+      std::vector<int> live;
+      for (int l = 0; l < n; ++l)
+        if (!std::binary_search(es->keys[id].begin(), es->keys[id].end(), l)) live.push_back(l);
+      survivor_runs[id] = runs_of(live.data(), static_cast<int>(live.size()));
+    }
+    auto reads = [&](size_t s) -> const std::vector<RowRun>& { return es ? survivor_runs[es->pat[s]] : all_rows; };
     auto writes = [&](size_t) -> int { return 0; };
     auto compute = [&](hipStream_t hs, size_t s0, size_t ns, uint8_t* dimg, size_t img_stripe, size_t dpitch, uint8_t*,
                        size_t) -> hrs_status {
@@ -1020,9 +1056,12 @@ hrs_status scrub_batch_host_impl(hrs_codec* c, const uint8_t* stripes, size_t ro
       const hipError_t e = hipMemcpy(chunk_rep.data(), drep + s0 * nwords, ns * nwords * sizeof(uint32_t),
                                      hipMemcpyDeviceToHost);
       if (e != hipSuccess) return hip_fail(c, e, "hipMemcpy chunk reports");
-      for (size_t i = 0; i < ns; ++i)
+      for (size_t i = 0; i < ns; ++i) {
+        if (es)  // the rebuilt cells (never blamed: their count is 0)
+          for (int l : es->keys[es->pat[s0 + i]]) cells.push_back({i, l});
         for (int l = 0; l < n; ++l)
           if (chunk_rep[i * nwords + hrs::kScrubHead + l] != 0) cells.push_back({i, l});
+      }
       return HRS_OK;
     };
     st = heal ? host_batch(c, stripes, row_stride, stripe_stride, n, const_cast<uint8_t*>(stripes), row_stride,
@@ -1041,12 +1080,20 @@ hrs_status scrub_batch_host_impl(hrs_codec* c, const uint8_t* stripes, size_t ro
 }
 
 // hrs_scrub_batch_host and hrs_heal_batch_host: one set of argument rules.
+// with_erased (hrs_heal_erased_batch_host[_crc]; heal is set): the erased
+// list's rules follow the sibling's, before the empty batch as in
+// hrs_heal_erased_dev, so a bad list is refused before any copy.
 hrs_status scrub_batch_host_entry(hrs_codec* c, const uint8_t* stripes, size_t row_stride, size_t stripe_stride,
                                   size_t len, size_t nstripes, uint32_t* reports, size_t report_stride, bool heal,
                                   bool with_crc = false, const uint32_t* crc_in = nullptr,
-                                  uint32_t* crc_out = nullptr) {
-  hrs_status st = scrub_args_ok(c, stripes, reports, report_stride, len, nstripes, kScrubWithReports | kScrubImage);
-  if (st != HRS_OK || nstripes == 0 || len == 0) return st;
+                                  uint32_t* crc_out = nullptr, bool with_erased = false, const int* erased = nullptr,
+                                  int max_erased = 0) {
+  hrs_status st = scrub_args_ok(c, stripes, reports, report_stride, len, nstripes, kScrubWithReports | kScrubImage,
+                                with_erased ? "max_erased" : nullptr, max_erased, erased);
+  if (st != HRS_OK) return st;
+  ErasedSets es;
+  if (with_erased && (st = erased_sets(c, erased, max_erased, nstripes, es)) != HRS_OK) return st;
+  if (nstripes == 0 || len == 0) return HRS_OK;
   // A read-only pass over a mis-strided batch would report "clean" or "bad"
   // with no error: the cells must not overlap. Rows of a stripe packed inside
   // the stripe stride, or stripes of a row packed inside the row stride.
@@ -1062,8 +1109,9 @@ hrs_status scrub_batch_host_entry(hrs_codec* c, const uint8_t* stripes, size_t r
     if (!crc_arrays_apart(crc_in, crc_out, nstripes * static_cast<size_t>(c->n)))
       return fail(c, HRS_EINVAL, "crc_in and crc_out overlap (crc_out may only be crc_in itself)");
   }
+  // max_erased == 0: nothing can be erased, the heal itself
   st = scrub_batch_host_impl(c, stripes, row_stride, stripe_stride, len, nstripes, reports, report_stride, heal,
-                             crc_in, crc_out);
+                             crc_in, crc_out, with_erased && max_erased > 0 ? &es : nullptr);
   if (st == HRS_OK) {
     DeviceGuard g(c->device);
     c->last_host_path =
@@ -1098,6 +1146,21 @@ hrs_status hrs_heal_batch_host_crc(hrs_codec* c, uint8_t* stripes, size_t row_st
                                    uint32_t* crc_out) {
   return scrub_batch_host_entry(c, stripes, row_stride, stripe_stride, len, nstripes, reports, report_stride, true,
                                 true, crc_in, crc_out);
+}
+
+hrs_status hrs_heal_erased_batch_host(hrs_codec* c, uint8_t* stripes, size_t row_stride, size_t stripe_stride,
+                                      size_t len, size_t nstripes, const int* erased, int max_erased,
+                                      uint32_t* reports, size_t report_stride) {
+  return scrub_batch_host_entry(c, stripes, row_stride, stripe_stride, len, nstripes, reports, report_stride, true,
+                                false, nullptr, nullptr, true, erased, max_erased);
+}
+
+hrs_status hrs_heal_erased_batch_host_crc(hrs_codec* c, uint8_t* stripes, size_t row_stride, size_t stripe_stride,
+                                          size_t len, size_t nstripes, const int* erased, int max_erased,
+                                          uint32_t* reports, size_t report_stride, const uint32_t* crc_in,
+                                          uint32_t* crc_out) {
+  return scrub_batch_host_entry(c, stripes, row_stride, stripe_stride, len, nstripes, reports, report_stride, true,
+                                true, crc_in, crc_out, true, erased, max_erased);
 }
 
 hrs_status hrs_decode_batch_dev(hrs_codec* c, const uint8_t* stripes, size_t row_stride, size_t stripe_stride,

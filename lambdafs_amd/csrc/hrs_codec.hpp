@@ -13,6 +13,7 @@
 
 #include "../../include/hrs.h"
 #include "crc32.hpp"
+#include "hrs_heal_erased.hpp"
 #include "hrs_internal.hpp"
 
 namespace hrs {
@@ -297,6 +298,39 @@ hrs_status run_scrub_crc(hrs_codec* c, const uint8_t* const* rows, size_t stride
 // 2 <= p <= 4, n <= 16, whole 2 KiB windows, 16-byte aligned rows and stride,
 // kernel mode 0 or 3.
 bool scrub_crc_one_pass(const hrs_codec* c, const uint8_t* const* rows, size_t stride, size_t len);
+
+// ---- heal with known erasures (hrs_scrub_api.cpp)
+// The erased set of one stripe: entries up to the first negative one (or
+// `cap`), sorted ascending into `key`. HRS_EINVAL for a location outside
+// [0, n) or a repeated one, HRS_ETOOMANY for more than p, the stripe named.
+hrs_status erased_key(hrs_codec* c, const int* erased, int cap, size_t stripe, std::vector<int>& key);
+// The device table entry of an erased set (hrs_heal_erased.hpp).
+hrs::ErasePattern make_pattern(int p, const std::vector<int>& key);
+// The erased sets of a batch, validated and de-duplicated: the table entries,
+// each entry's locations (ascending) and every stripe's entry. max_erased <= 0
+// leaves all three empty.
+struct ErasedSets {
+  std::vector<hrs::ErasePattern> pats;
+  std::vector<std::vector<int>> keys;
+  std::vector<int32_t> pat;
+};
+hrs_status erased_sets(hrs_codec* c, const int* erased, int max_erased, size_t nstripes, ErasedSets& es);
+// hrs_heal_erased_dev after its checks: uploads the table and pat[nstripes]
+// through a batch slot on s, then the window and tail kernels.
+hrs_status run_heal_erased(hrs_codec* c, uint8_t* const* rows, size_t stride, size_t len, size_t nstripes,
+                           const std::vector<hrs::ErasePattern>& pats, const int32_t* pat, uint32_t* reports,
+                           size_t report_stride, hipStream_t s);
+// run_heal_erased plus the CRC-32 of every cell as the call leaves it
+// (crc_out[s * n + l], hops order, DEVICE arrays). One pass
+// (hrs_heal_erased_crc.hip) for the shapes of scrub_crc_one_pass in kernel
+// mode 3, and in mode 0 where heal_erased_crc_fused_default says so for the
+// memory the rows lie in; else run_heal_erased, then the CRC pass over the n
+// rows. Takes and releases the handle's raw-CRC scratch on stream s.
+hrs_status run_heal_erased_crc(hrs_codec* c, uint8_t* const* rows, size_t stride, size_t len, size_t nstripes,
+                               const std::vector<hrs::ErasePattern>& pats, const int32_t* pat, uint32_t* reports,
+                               size_t report_stride, const uint32_t* crc_in, uint32_t* crc_out, hipStream_t s,
+                               bool host_memory);
+bool heal_erased_crc_fused_default(bool host_memory);
 
 // ---- per-call device tables (hrs_batch_api.cpp)
 // The next of the handle's two batch slots (pinned staging `host` + device

@@ -170,4 +170,16 @@ struct ScrubCrcArgs {
 hipError_t launch_scrub_crc(const ScrubCrcArgs& a, bool heal, int cus, hipStream_t s);
 hipError_t launch_scrub_crc_redo(const ScrubCrcArgs& a, int cus, hipStream_t s);
 
+// Fused heal with known erasures + CRC-32 (hrs_heal_erased_crc.hip):
+// heal_erased_kernel's walk with the raw window CRCs of ScrubCrcArgs, same
+// shapes. Every window with a bad column is listed in c.dirty (zeroed by the
+// caller), and launch_scrub_crc_redo(c) after it rewrites those windows' words.
+struct ErasePattern;  // hrs_heal_erased.hpp
+struct HealErasedCrcArgs {
+  ScrubCrcArgs c;            // rows are written: erased cells filled, survivors patched
+  const ErasePattern* pats;  // device table
+  const int32_t* pat;        // device: pattern index of each stripe
+};
+hipError_t launch_heal_erased_crc(const HealErasedCrcArgs& a, int cus, hipStream_t s);
+
 }  // namespace hrs

@@ -2,10 +2,11 @@
 // computeErrorLocations on the host (hrs_compute_error_locations, host-only
 // handles included), the device-resident batches (hrs_scrub_dev, hrs_heal_dev,
 // hrs_scrub_crc_dev, hrs_heal_crc_dev with the cells' CRC-32s from the same
-// pass, and hrs_heal_erased_dev with its erasure patterns: validated,
-// de-duplicated, with the constants the kernels of hrs_heal_erased.hip
-// multiply by) and one stripe healed on the CPU (hrs_heal_host,
-// hrs_heal_erased_host), the kernels' byte-exact reference. The host-memory
+// pass, and hrs_heal_erased_dev / hrs_heal_erased_crc_dev with their erasure
+// patterns: validated, de-duplicated, with the constants the kernels of
+// hrs_heal_erased.hip and hrs_heal_erased_crc.hip multiply by) and one stripe
+// healed on the CPU (hrs_heal_host, hrs_heal_erased_host), the kernels'
+// byte-exact reference. The host-memory
 // batches are in hrs_batch_api.cpp beside the pipeline they share. The
 // per-column algorithm is hrs_locator.hpp, the same code the kernels run.
 //
@@ -286,6 +287,8 @@ hrs_status scrub_crc_dev_entry(hrs_codec* c, const uint8_t* const* rows, size_t 
                        static_cast<hipStream_t>(stream), heal);
 }
 
+}  // namespace
+
 // ---- heal with known erasures
 
 // The erased set of one stripe: entries up to the first negative one (or
@@ -334,28 +337,173 @@ hrs::ErasePattern make_pattern(int p, const std::vector<int>& key) {
   return pt;
 }
 
-hrs_status run_heal_erased(hrs_codec* c, uint8_t* const* rows, size_t stride, size_t len, size_t nstripes,
-                           const std::vector<hrs::ErasePattern>& pats, const std::vector<int32_t>& pat,
-                           uint32_t* reports, size_t report_stride, hipStream_t s) {
+// The erased sets of a batch, validated and de-duplicated (stripe by stripe,
+// so the first bad stripe is the one named).
+hrs_status erased_sets(hrs_codec* c, const int* erased, int max_erased, size_t nstripes, ErasedSets& es) {
+  es.pats.clear();
+  es.keys.clear();
+  es.pat.assign(max_erased > 0 ? nstripes : 0, 0);
+  if (max_erased <= 0) return HRS_OK;
+  std::map<std::vector<int>, int32_t> ids;
+  std::vector<int> key;
+  for (size_t s = 0; s < nstripes; ++s) {
+    const hrs_status st = erased_key(c, erased + s * static_cast<size_t>(max_erased), max_erased, s, key);
+    if (st != HRS_OK) return st;
+    auto it = ids.find(key);
+    if (it == ids.end()) {
+      it = ids.emplace(key, static_cast<int32_t>(es.pats.size())).first;
+      es.pats.push_back(make_pattern(c->p, key));
+      es.keys.push_back(key);
+    }
+    es.pat[s] = it->second;
+  }
+  return HRS_OK;
+}
+
+namespace {
+
+// The pattern table and the pattern indices of `nstripes` stripes into the
+// next batch slot and up to the device on s. The caller records the slot's
+// event after its launches (slot_used).
+hrs_status upload_patterns(hrs_codec* c, const std::vector<hrs::ErasePattern>& pats, const int32_t* pat,
+                           size_t nstripes, hipStream_t s, hrs_codec::BatchSlot** slot,
+                           const hrs::ErasePattern** dpats, const int32_t** dpat) {
   const size_t pat_bytes = pats.size() * sizeof(hrs::ErasePattern);
-  const size_t need = pat_bytes + pat.size() * sizeof(int32_t);
-  hrs_codec::BatchSlot* sl = nullptr;
-  hrs_status st = batch_slot_acquire(c, need, &sl);
+  const size_t need = pat_bytes + nstripes * sizeof(int32_t);
+  hrs_status st = batch_slot_acquire(c, need, slot);
   if (st != HRS_OK) return st;
+  hrs_codec::BatchSlot* sl = *slot;
   std::memcpy(sl->host, pats.data(), pat_bytes);
-  std::memcpy(sl->host + pat_bytes, pat.data(), pat.size() * sizeof(int32_t));
+  std::memcpy(sl->host + pat_bytes, pat, nstripes * sizeof(int32_t));
   const hipError_t e = hipMemcpyAsync(sl->dev, sl->host, need, hipMemcpyHostToDevice, s);
   if (e != hipSuccess) return hip_fail(c, e, "hipMemcpyAsync patterns");
+  *dpats = reinterpret_cast<const hrs::ErasePattern*>(sl->dev);
+  *dpat = reinterpret_cast<const int32_t*>(sl->dev + pat_bytes);
+  return HRS_OK;
+}
+
+// the slot's table may be in use whether or not every launch went out
+void slot_used(hrs_codec::BatchSlot* sl, hipStream_t s) {
+  if (hipEventRecord(sl->done, s) == hipSuccess) sl->pending = true;
+  else (void)hipStreamSynchronize(s);
+}
+
+}  // namespace
+
+hrs_status run_heal_erased(hrs_codec* c, uint8_t* const* rows, size_t stride, size_t len, size_t nstripes,
+                           const std::vector<hrs::ErasePattern>& pats, const int32_t* pat, uint32_t* reports,
+                           size_t report_stride, hipStream_t s) {
+  hrs_codec::BatchSlot* sl = nullptr;
   hrs::HealErasedArgs a{};
-  a.pats = reinterpret_cast<const hrs::ErasePattern*>(sl->dev);
-  a.pat = reinterpret_cast<const int32_t*>(sl->dev + pat_bytes);
+  hrs_status st = upload_patterns(c, pats, pat, nstripes, s, &sl, &a.pats, &a.pat);
+  if (st != HRS_OK) return st;
   st = run_windows_tail(
       c, a.s, rows, stride, len, nstripes, reports, report_stride, s, "heal erased",
       [&] { return hrs::launch_heal_erased(a, s); }, [&] { return hrs::launch_heal_erased_bytewise(a, s); });
-  // the slot's table may be in use whether or not every launch went out
-  if (hipEventRecord(sl->done, s) == hipSuccess) sl->pending = true;
-  else (void)hipStreamSynchronize(s);
+  slot_used(sl, s);
   return st;
+}
+
+// Kernel mode 0: whether a fused shape takes heal_erased_crc_kernel<P>. Mode
+// 3 always does, mode 2 never. Measured (DESIGN 10.4,
+// profiles/heal_erased/bench_heal_erased_crc.json): over pinned host memory
+// the fused call takes 0.483 of the plain call plus a second zero-copy read,
+// the ranges far apart; on device-resident stripes it ran at 1.006 of the two
+// passes with overlapping ranges, so those keep the two passes.
+bool heal_erased_crc_fused_default(bool host_memory) { return host_memory; }
+
+hrs_status run_heal_erased_crc(hrs_codec* c, uint8_t* const* rows, size_t stride, size_t len, size_t nstripes,
+                               const std::vector<hrs::ErasePattern>& pats, const int32_t* pat, uint32_t* reports,
+                               size_t report_stride, const uint32_t* crc_in, uint32_t* crc_out, hipStream_t s,
+                               bool host_memory) {
+  const int n = c->n;
+  const bool fused = scrub_crc_one_pass(c, rows, stride, len) &&
+                     (c->kernel_mode == 3 || heal_erased_crc_fused_default(host_memory));
+  if (!fused) {
+    // two passes: the heal as it is, then the CRC of the n rows (the stream
+    // orders the heal's stores before the CRC pass reads them)
+    hrs_status st = run_heal_erased(c, rows, stride, len, nstripes, pats, pat, reports, report_stride, s);
+    if (st != HRS_OK) return st;
+    const std::string kernel = c->last_kernel;
+    st = crc_scratch(c, crc_raw_bytes_for(len, nstripes, n), s);
+    if (st != HRS_OK) return st;
+    const std::vector<size_t> strides(n, stride);
+    st = crc_scratch_release(c, s, run_crc(c, rows, strides.data(), n, len, nstripes, crc_in, crc_out, s, c->crc_raw));
+    c->last_kernel = kernel;
+    return st;
+  }
+  hipError_t e = hrs::launch_scrub_init(reports, report_stride, n, nstripes, s);
+  if (e != hipSuccess) return hip_fail(c, e, "scrub init launch");
+  hrs_status st = crc_window_tables(c);
+  if (st != HRS_OK) return st;
+  hrs::HealErasedCrcArgs a{};
+  for (int l = 0; l < n; ++l) a.c.rows[l] = rows[l];
+  a.c.stride = stride;
+  a.c.nwin = len / hrs::kWindowBytes;
+  a.c.ntasks = a.c.nwin * nstripes;
+  a.c.reports = reports;
+  a.c.report_stride = report_stride;
+  a.c.n = n;
+  a.c.p = c->p;
+  a.c.tables = c->crc_tables_a;
+  hrs_codec::BatchSlot* sl = nullptr;
+  st = upload_patterns(c, pats, pat, nstripes, s, &sl, &a.pats, &a.pat);
+  if (st != HRS_OK) return st;
+  // scratch: the raw window CRCs, then the dirty-task count and list
+  const size_t raw_bytes = (a.c.ntasks * static_cast<size_t>(n) * 4 + 7) & ~static_cast<size_t>(7);
+  const size_t list_bytes = (1 + a.c.ntasks) * sizeof(uint64_t);
+  st = crc_scratch(c, raw_bytes + list_bytes, s);
+  if (st != HRS_OK) {
+    slot_used(sl, s);
+    return st;
+  }
+  a.c.raw = c->crc_raw;
+  a.c.dirty = reinterpret_cast<uint64_t*>(reinterpret_cast<uint8_t*>(c->crc_raw) + raw_bytes);
+  const int cus = hrs::device_cu_count();
+  auto launches = [&]() -> hrs_status {
+    if ((e = hipMemsetAsync(a.c.dirty, 0, sizeof(uint64_t), s)) != hipSuccess) return hip_fail(c, e, "hipMemsetAsync");
+    if ((e = hrs::launch_heal_erased_crc(a, cus, s)) != hipSuccess) return hip_fail(c, e, "heal erased+crc launch");
+    c->last_kernel = hrs::last_kernel();
+    if ((e = hrs::launch_scrub_crc_redo(a.c, cus, s)) != hipSuccess) return hip_fail(c, e, "crc redo launch");
+    return crc_fold_windows(c, len, nstripes * static_cast<uint64_t>(n), crc_in, crc_out, s, c->crc_raw,
+                            hrs::kWindowBytes);
+  };
+  st = crc_scratch_release(c, s, launches());
+  slot_used(sl, s);
+  return st;
+}
+
+namespace {
+
+// hrs_heal_erased_dev and hrs_heal_erased_crc_dev (with_crc): the heal's
+// argument rules with the erased list's, the erased sets, the empty batch,
+// then the CRC arrays' rules, then the device.
+hrs_status heal_erased_dev_entry(hrs_codec* c, uint8_t* const* rows, size_t stride, size_t len, size_t nstripes,
+                                 const int* erased, int max_erased, uint32_t* reports, size_t report_stride,
+                                 bool with_crc, const uint32_t* crc_in, uint32_t* crc_out, void* stream) {
+  hrs_status st = scrub_args_ok(c, rows, reports, report_stride, len, nstripes, kScrubWithReports | kScrubRowsWritten,
+                                "max_erased", max_erased, erased);
+  if (st != HRS_OK) return st;
+  ErasedSets es;
+  st = erased_sets(c, erased, max_erased, nstripes, es);
+  if (st != HRS_OK) return st;
+  if (len == 0 || nstripes == 0) return HRS_OK;
+  if (with_crc) {
+    if (!crc_out) return fail(c, HRS_EINVAL, "crc_out is NULL");
+    if (!crc_arrays_apart(crc_in, crc_out, nstripes * static_cast<size_t>(c->n)))
+      return fail(c, HRS_EINVAL, "crc_in and crc_out overlap (crc_out may only be crc_in itself)");
+  }
+  DeviceGuard g(c->device);
+  if (!g.ok) return fail(c, HRS_EDEVICE, "cannot select HIP device %d", c->device);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (max_erased == 0) {  // nothing can be erased: the heal itself
+    if (!with_crc) return run_scrub(c, rows, stride, len, nstripes, reports, report_stride, s, true);
+    return run_scrub_crc(c, rows, stride, len, nstripes, reports, report_stride, crc_in, crc_out, s, true);
+  }
+  if (!with_crc)
+    return run_heal_erased(c, rows, stride, len, nstripes, es.pats, es.pat.data(), reports, report_stride, s);
+  return run_heal_erased_crc(c, rows, stride, len, nstripes, es.pats, es.pat.data(), reports, report_stride, crc_in,
+                             crc_out, s, false);
 }
 
 }  // namespace
@@ -428,32 +576,15 @@ hrs_status hrs_heal_host(const hrs_codec* cc, uint8_t* const* rows, size_t len, 
 hrs_status hrs_heal_erased_dev(hrs_codec* c, uint8_t* const* rows, size_t stride, size_t len, size_t nstripes,
                                const int* erased, int max_erased, uint32_t* reports, size_t report_stride,
                                void* stream) {
-  hrs_status st = scrub_args_ok(c, rows, reports, report_stride, len, nstripes, kScrubWithReports | kScrubRowsWritten,
-                                "max_erased", max_erased, erased);
-  if (st != HRS_OK) return st;
-  std::vector<hrs::ErasePattern> pats;
-  std::vector<int32_t> pat(max_erased > 0 ? nstripes : 0, 0);
-  if (max_erased > 0) {
-    std::map<std::vector<int>, int32_t> ids;
-    std::vector<int> key;
-    for (size_t s = 0; s < nstripes; ++s) {
-      st = erased_key(c, erased + s * static_cast<size_t>(max_erased), max_erased, s, key);
-      if (st != HRS_OK) return st;
-      auto it = ids.find(key);
-      if (it == ids.end()) {
-        it = ids.emplace(key, static_cast<int32_t>(pats.size())).first;
-        pats.push_back(make_pattern(c->p, key));
-      }
-      pat[s] = it->second;
-    }
-  }
-  if (len == 0 || nstripes == 0) return HRS_OK;
-  DeviceGuard g(c->device);
-  if (!g.ok) return fail(c, HRS_EDEVICE, "cannot select HIP device %d", c->device);
-  hipStream_t s = static_cast<hipStream_t>(stream);
-  if (max_erased == 0)  // nothing can be erased: the heal itself
-    return run_scrub(c, rows, stride, len, nstripes, reports, report_stride, s, true);
-  return run_heal_erased(c, rows, stride, len, nstripes, pats, pat, reports, report_stride, s);
+  return heal_erased_dev_entry(c, rows, stride, len, nstripes, erased, max_erased, reports, report_stride, false,
+                               nullptr, nullptr, stream);
+}
+
+hrs_status hrs_heal_erased_crc_dev(hrs_codec* c, uint8_t* const* rows, size_t stride, size_t len, size_t nstripes,
+                                   const int* erased, int max_erased, uint32_t* reports, size_t report_stride,
+                                   const uint32_t* crc_in, uint32_t* crc_out, void* stream) {
+  return heal_erased_dev_entry(c, rows, stride, len, nstripes, erased, max_erased, reports, report_stride, true,
+                               crc_in, crc_out, stream);
 }
 
 hrs_status hrs_heal_erased_host(const hrs_codec* cc, uint8_t* const* rows, size_t len, const int* erased,

@@ -549,6 +549,84 @@ def heal_erased_host(code, rows, erased):
     return report
 
 
+def _heal_erased_crc(code, rows, stride, L, S, ref, erased, crc_in):
+    torch = _lib.torch
+    n = code.stripeSize() + code.paritySize()
+    arr = _erased_array(erased, S)
+    reports = torch.empty((S, SCRUB_HEAD + n), dtype=torch.int32, device=ref.device)
+    crc = torch.empty((S, n), dtype=torch.int32, device=ref.device)
+    cin = None
+    if crc_in is not None:
+        if crc_in.shape != crc.shape or crc_in.dtype != torch.int32 or not crc_in.is_contiguous() \
+                or crc_in.device != ref.device:
+            raise ValueError(f"crc_in must be a contiguous int32 device tensor [S, {n}]")
+        cin = crc_in.data_ptr()
+    if L == 0 or S == 0:  # the call touches nothing: every CRC continues over no bytes
+        crc.zero_() if crc_in is None else crc.copy_(crc_in)
+    code._check(_lib.lib().hrs_heal_erased_crc_dev(code._handle(), rows, stride, L, S, arr.ctypes.data, arr.shape[1],
+                                                   reports.data_ptr(), SCRUB_HEAD + n, cin, crc.data_ptr(),
+                                                   _stream(ref)))
+    return reports, crc
+
+
+def heal_erased_stripes_crc(code, stripes, erased, crc_in=None):
+    """heal_erased_stripes plus the CRC-32 of every cell AS THE CALL LEAVES IT
+    (hrs_heal_erased_crc_dev): rebuilt cells, patched survivors, unresolved
+    columns as they were. Returns (reports, crcs), crcs an int32 tensor [S, n]
+    of the uint32 CRC bits in HOPS order as heal_stripes_crc returns them;
+    crc_in ([S, n] int32) continues running CRCs. A stripe whose CRCs equal its
+    stored checksums was restored."""
+    n = code.stripeSize() + code.paritySize()
+    if stripes.dim() != 3 or stripes.shape[1] != n:
+        raise ValueError(f"stripes must be [S, {n}, L]")
+    rows, stride, L, S = _stripe_rows(stripes, range(n))
+    return _heal_erased_crc(code, rows, stride, L, S, stripes, erased, crc_in)
+
+
+def heal_erased_rows_crc(code, row_views, erased, crc_in=None):
+    """heal_erased_stripes_crc with explicit [S, L] row views, one per location in hops order."""
+    n = code.stripeSize() + code.paritySize()
+    if len(row_views) != n or any(v is None for v in row_views):
+        raise ValueError(f"need {n} row views")
+    rows, stride, L, S = _rows(row_views)
+    return _heal_erased_crc(code, rows, stride, L, S, row_views[0], erased, crc_in)
+
+
+def _heal_erased_batch_host(code, stripes, erased, with_crc, crc_in=None, crc_out=None):
+    n = code.stripeSize() + code.paritySize()
+    sp, sshape, sstr = _host_ptr(stripes, "stripes", writable=True)
+    if len(sshape) != 3 or sshape[1] != n or sstr[2] != 1:
+        raise ValueError(f"stripes must be [S, {n}, L] with unit byte stride")
+    S, L = sshape[0], sshape[2]
+    arr = _erased_array(erased, S)
+    reports = np.zeros((S, SCRUB_HEAD + n), dtype=np.uint32)
+    if not with_crc:
+        code._check(_lib.lib().hrs_heal_erased_batch_host(code._handle(), sp, sstr[1], sstr[0], L, S, arr.ctypes.data,
+                                                          arr.shape[1], reports.ctypes.data, SCRUB_HEAD + n))
+        return reports
+    cin, crc = _host_crcs((S, n), L, crc_in, crc_out)
+    code._check(_lib.lib().hrs_heal_erased_batch_host_crc(code._handle(), sp, sstr[1], sstr[0], L, S, arr.ctypes.data,
+                                                          arr.shape[1], reports.ctypes.data, SCRUB_HEAD + n, cin,
+                                                          crc.ctypes.data))
+    return reports, crc
+
+
+def heal_erased_batch_host(code, stripes, erased):
+    """hrs_heal_erased_batch_host: heal_erased_stripes for stripes[S, n, L] in
+    HOST memory (numpy array or CPU tensor, healed in place; of staged memory
+    only the survivors are copied in, and only the erased cells and the cells
+    that held a resolved error are written): a numpy uint32 array [S, 4 + n].
+    erased as for heal_erased_stripes."""
+    return _heal_erased_batch_host(code, stripes, erased, False)
+
+
+def heal_erased_batch_host_crc(code, stripes, erased, crc_in=None, crc_out=None):
+    """hrs_heal_erased_batch_host_crc: heal_erased_batch_host plus the CRC-32
+    of every cell as the call leaves it: (reports, crcs), crcs a numpy uint32
+    array [S, n] in HOPS order; crc_in and crc_out as for heal_batch_host_crc."""
+    return _heal_erased_batch_host(code, stripes, erased, True, crc_in, crc_out)
+
+
 def scrub_to_erased(reports, p):
     """The int32 [S, p] erasure array decode_batch takes from scrub reports
     [S, 4 + n]: per stripe the locations with a nonzero count, ascending, -1
@@ -662,7 +740,9 @@ def heal_batch_host_crc(code, stripes, crc_in=None, crc_out=None):
 
 
 def checksums_to_erased(crcs, stored, p, reports=None):
-    """The int32 [S, p] erasure array decode_batch / decode_batch_crc take, from
+    """The int32 [S, p] erasure array decode_batch / decode_batch_crc and the
+    heal-with-erasures calls (heal_erased_stripes[_crc], heal_erased_rows[_crc],
+    heal_erased_batch_host[_crc]) take, from
     the cell CRCs of a scrub ([S, n], hops order) and the stored checksums:
     per stripe the locations whose CRC differs from `stored`, joined, when
     `reports` ([S, 4 + n]) is given, by the locations with a nonzero count in
