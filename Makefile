@@ -12,16 +12,18 @@ ORACLE   := oracle/liboracle.so
 HDRS     := Makefile include/hrs.h lambdafs_amd/csrc/hrs_device.hpp lambdafs_amd/csrc/hrs_launch.hpp lambdafs_amd/csrc/gf256.hpp lambdafs_amd/csrc/hrs_internal.hpp \
             lambdafs_amd/csrc/crc32.hpp lambdafs_amd/csrc/hrs_crc.hpp lambdafs_amd/csrc/xor_sched.hpp lambdafs_amd/csrc/hrs_codec.hpp \
             lambdafs_amd/csrc/hrs_host.hpp lambdafs_amd/csrc/hrs_locator.hpp lambdafs_amd/csrc/hrs_heal_erased.hpp \
-            lambdafs_amd/csrc/hrs_scrub_device.hpp
+            lambdafs_amd/csrc/hrs_scrub_device.hpp lambdafs_amd/csrc/hrs_repair.hpp lambdafs_amd/csrc/hrs_repair_rule.hpp
 
 # Host translation units of the C ABI (no kernels): lifecycle + queries,
-# matrices, device dispatch + CRC, host-buffer path, batches, scrubbing.
-API_SRC  := hrs_api hrs_matrix hrs_dispatch hrs_hostpath hrs_batch_api hrs_scrub_api
+# matrices, device dispatch + CRC, host-buffer path, batches, scrubbing,
+# checked repair.
+API_SRC  := hrs_api hrs_matrix hrs_dispatch hrs_hostpath hrs_batch_api hrs_scrub_api hrs_repair_api
 API_OBJ  := $(patsubst %,build/%.o,$(API_SRC))
 
 JNI      := lambdafs_amd/libhrs_jni.so
 HARNESS  := tests/cpp/codec_harness tests/cpp/crc_model tests/cpp/jni_harness tests/cpp/host_logic tests/cpp/crc_tables \
-            tests/cpp/copy_pool_test tests/cpp/scrub_logic tests/cpp/heal_logic tests/cpp/heal_erased_logic
+            tests/cpp/copy_pool_test tests/cpp/scrub_logic tests/cpp/heal_logic tests/cpp/heal_erased_logic \
+            tests/cpp/repair_checked_logic
 
 TOOLS    := tools/host_call_rate tools/host_pipeline_sweep tools/host_copy_probe
 
@@ -57,7 +59,7 @@ build/hrs_fused.o: HIPFLAGS += -mllvm -pragma-unroll-threshold=1000000
 build/hrs_probe.o: include/hrs_probe.h
 
 # `make scrub_resources`, `make scrub_crc_resources`, `make heal_erased_resources`,
-# `make heal_erased_crc_resources`:
+# `make heal_erased_crc_resources`, `make repair_resources`:
 # the compiler's resource report of every kernel of hrs_<name>.hip (the scrub
 # family carries no scratch). Not .PHONY: a phony target takes no pattern rule.
 %_resources: lambdafs_amd/csrc/hrs_%.hip $(HDRS)
@@ -67,7 +69,7 @@ build/hrs_probe.o: include/hrs_probe.h
 
 KOBJ     := build/hrs_kernels.o build/hrs_runtime.o build/hrs_batch.o build/hrs_crc.o build/hrs_fused.o build/hrs_decode_crc.o \
             build/hrs_batch_crc.o build/hrs_gate.o build/hrs_scrub.o build/hrs_scrub_crc.o build/hrs_heal_erased.o \
-            build/hrs_heal_erased_crc.o
+            build/hrs_heal_erased_crc.o build/hrs_repair.o
 
 $(LIB): $(API_OBJ) $(KOBJ) lambdafs_amd/csrc/libhrs.map
 	$(HIPCC) $(HIPFLAGS) -shared -Wl,--version-script=lambdafs_amd/csrc/libhrs.map -o $@ $(API_OBJ) $(KOBJ) \
@@ -117,6 +119,13 @@ tests/cpp/heal_erased_logic: tests/cpp/heal_erased_logic.cpp include/hrs.h $(LIB
 	g++ -O2 -std=c++17 -Wall -Iinclude -Ioracle -o $@ $< -Llambdafs_amd -lhrs -Loracle -loracle \
 	    -Wl,-rpath,'$$ORIGIN/../../lambdafs_amd' -Wl,-rpath,'$$ORIGIN/../../oracle'
 
+# Checked repair on the CPU (hrs_repair_checked_host) and the pattern builder the plan kernel shares
+# (hrs_repair_rule.hpp) against a construction of its own.
+tests/cpp/repair_checked_logic: tests/cpp/repair_checked_logic.cpp include/hrs.h lambdafs_amd/csrc/hrs_repair_rule.hpp \
+                                lambdafs_amd/csrc/hrs_heal_erased.hpp lambdafs_amd/csrc/hrs_locator.hpp $(LIB)
+	g++ -O2 -std=c++17 -Wall -D__HIP_PLATFORM_AMD__ -Iinclude -I/opt/rocm/include -o $@ $< -Llambdafs_amd -lhrs -lz \
+	    -Wl,-rpath,'$$ORIGIN/../../lambdafs_amd'
+
 # The CRC tables the kernels load, dumped for tests/test_crc_tables.py (host code;
 # hipcc only for the HIP headers hrs_crc.hpp includes).
 tests/cpp/crc_tables: tests/cpp/crc_tables.cpp lambdafs_amd/csrc/crc32.hpp lambdafs_amd/csrc/hrs_crc.hpp
@@ -140,7 +149,7 @@ SAN      := -fsanitize=address,undefined -fno-sanitize-recover=undefined -fno-om
 HSAN     := -Xarch_host -fsanitize=address -Xarch_host -fsanitize=undefined -Xarch_host -fno-sanitize-recover=undefined \
             -Xarch_host -fno-omit-frame-pointer
 ASAN_BIN := $(ASAN_DIR)/host_logic $(ASAN_DIR)/jni_harness $(ASAN_DIR)/codec_harness $(ASAN_DIR)/scrub_logic \
-            $(ASAN_DIR)/heal_logic $(ASAN_DIR)/heal_erased_logic
+            $(ASAN_DIR)/heal_logic $(ASAN_DIR)/heal_erased_logic $(ASAN_DIR)/repair_checked_logic
 ASAN_LOG := profiles/r06/asan
 
 ASAN_API := $(patsubst %,$(ASAN_DIR)/%.o,$(API_SRC))
@@ -171,6 +180,9 @@ $(ASAN_DIR)/heal_logic: tests/cpp/heal_logic.cpp $(ASAN_DIR)/libhrs.so $(ASAN_DI
 $(ASAN_DIR)/heal_erased_logic: tests/cpp/heal_erased_logic.cpp $(ASAN_DIR)/libhrs.so $(ASAN_DIR)/liboracle.so
 	$(CLANG)++ $(SAN) -std=c++17 -Iinclude -Ioracle -o $@ $< -L$(ASAN_DIR) -lhrs -loracle $(ASAN_RPATH)
 
+$(ASAN_DIR)/repair_checked_logic: tests/cpp/repair_checked_logic.cpp $(ASAN_DIR)/libhrs.so
+	$(CLANG)++ $(SAN) -std=c++17 -D__HIP_PLATFORM_AMD__ -Iinclude -I/opt/rocm/include -o $@ $< -L$(ASAN_DIR) -lhrs -lz $(ASAN_RPATH)
+
 $(ASAN_DIR)/jni_harness: tests/cpp/jni_harness.c $(ASAN_DIR)/libhrs_jni.so $(ASAN_DIR)/liboracle.so
 	$(CLANG) $(SAN) -std=c11 -Iinclude -Ioracle -o $@ $< -L$(ASAN_DIR) -lhrs_jni -lhrs -loracle -lz -ldl $(ASAN_RPATH)
 
@@ -186,6 +198,7 @@ asan: $(ASAN_BIN)
 	  $(ASAN_DIR)/scrub_logic; \
 	  $(ASAN_DIR)/heal_logic; \
 	  $(ASAN_DIR)/heal_erased_logic; \
+	  $(ASAN_DIR)/repair_checked_logic; \
 	  $(ASAN_DIR)/jni_harness --cpu; \
 	  for kp in "10 4" "12 4" "6 3" "3 2"; do $(ASAN_DIR)/codec_harness --host-only $$kp; done' \
 	  > $(ASAN_LOG)/asan_run.log 2>&1 || { cat $(ASAN_LOG)/asan_run.log; exit 1; }

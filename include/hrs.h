@@ -756,6 +756,87 @@ hrs_status hrs_heal_erased_batch_host_crc(hrs_codec* codec, uint8_t* stripes, si
                                           uint32_t* reports, size_t report_stride, const uint32_t* crc_in,
                                           uint32_t* crc_out);
 
+/* ---- checked repair: stored checksums in, verdicts out ----
+ * The workflow of the reference's Decoder and BlockReconstructor as one call:
+ * a cell is first known to be bad by its block checksum (Decoder.java:373-387),
+ * it becomes an erased location, the stripe is repaired, and the repaired
+ * block is accepted by its checksum (Decoder.java:222-229, :645-655). Per
+ * stripe, with C_l the CRC-32 of cell l as read, stored_l the caller's
+ * checksum of it and R the stripe's hrs_scrub_dev report:
+ *   1. D = { l : C_l != stored_l };
+ *   2. B = D, or with HRS_REPAIR_JOIN_SYNDROMES B = D + { l : R[4 + l] != 0 };
+ *   3. in this order: D empty and R[1] > 0: HRS_REPAIR_AMBIGUOUS (unresolved
+ *      columns and no checksum differs); D empty and R[0] = 0:
+ *      HRS_REPAIR_CLEAN; |B| > parity_size: HRS_REPAIR_TOOMANY; otherwise the
+ *      stripe is listed with the erasure set E = B (E may be empty: without
+ *      the join flag, D empty, R[0] > 0 and R[1] = 0 runs the plain heal);
+ *   4. a clean, too-many or ambiguous stripe is never written and the second
+ *      pass never reads it: its report is R, its crc_out words are C, its
+ *      erased_out row is all -1;
+ *   5. a listed stripe gets exactly hrs_heal_erased_dev's bytes and report for
+ *      E; its erased_out row holds E ascending, -1 padded, and its crc_out
+ *      words the CRCs of the cells as the call leaves them;
+ *   6. with F = { l : crc_out_l != stored_l } and R' the listed stripe's
+ *      report: F empty: HRS_REPAIR_REPAIRED; F and D disjoint and R'[1] = 0:
+ *      HRS_REPAIR_RESTAMP (the stripe is a codeword and every checksum that
+ *      was doubted now matches; the cells in F held a matching checksum over
+ *      stale bytes, and crc_out has their new values); anything else:
+ *      HRS_REPAIR_FAILED, the bytes as hrs_heal_erased_dev leaves them.
+ * Every output is a function of the inputs alone. Checksums alone (flags 0)
+ * is the reference's rule and the default: a cell of whole-cell garbage puts
+ * more errors into every column than the locator resolves, the few columns it
+ * then mis-resolves blame cells that are sound, and the joined set can pass
+ * parity_size for damage that is inside the code's capacity (DESIGN.md
+ * section 10.5). The join flag is for few-column damage whose checksum was
+ * rewritten with it. Codes as for the scrub. */
+#define HRS_REPAIR_JOIN_SYNDROMES 1 /* flags bit 0 */
+enum {
+  HRS_REPAIR_CLEAN = 0,
+  HRS_REPAIR_REPAIRED = 1,
+  HRS_REPAIR_RESTAMP = 2,
+  HRS_REPAIR_FAILED = 3,
+  HRS_REPAIR_TOOMANY = 4,
+  HRS_REPAIR_AMBIGUOUS = 5
+};
+
+/* Device-resident batch. rows, stride, len, nstripes, reports, report_stride
+ * and stream as for hrs_heal_erased_dev (n DEVICE pointers in hops order, none
+ * NULL, no two equal). DEVICE arrays: stored, uint32 [nstripes * n], the fresh
+ * whole-cell CRC-32s in hops order like hrs_scrub_crc_dev's crc_out (there is
+ * no crc_in); crc_out, the same shape, which must not overlap stored
+ * (HRS_EINVAL); verdicts, uint32 [nstripes]; erased_out, int32
+ * [nstripes * parity_size], may be NULL. A flags bit other than bit 0 is
+ * HRS_EINVAL, and so is a NULL stored, verdicts, reports or crc_out with work
+ * to do. Argument errors come first; then len == 0 or nstripes == 0 returns
+ * HRS_OK and touches nothing; then the device is selected (HRS_EDEVICE for a
+ * host-only handle). Any alignment is accepted, by the siblings' split: vector
+ * kernels over the whole 2 KiB windows, byte-granular kernels over tails,
+ * unaligned layouts and kernel mode 2.
+ *
+ * Everything runs on stream with no host wait, no copy to the host and no
+ * host-built table between the passes: pass 1 is hrs_scrub_crc_dev as it is
+ * (hrs_last_kernel names its kernel); repair_plan_kernel applies steps 1-3,
+ * builds each listed stripe's erasure pattern on the device and appends the
+ * stripe to a list in the handle's scratch; pass 2 (heal_listed_kernel<P>,
+ * heal_listed_bytewise_kernel<P>: hrs_heal_erased_dev's kernels over the
+ * listed stripes only), the CRC pass and the verdicts take their task range
+ * from that list. The scratch holds one table entry of 128 bytes and one list
+ * word per stripe of the batch beside the raw window CRCs of pass 1.
+ * Asynchronous on stream. */
+hrs_status hrs_repair_checked_dev(hrs_codec* codec, uint8_t* const* rows, size_t stride, size_t len, size_t nstripes,
+                                  const uint32_t* stored, int flags, uint32_t* verdicts, int32_t* erased_out,
+                                  uint32_t* reports, size_t report_stride, uint32_t* crc_out, void* stream);
+
+/* The same operation for one stripe of n HOST rows on the CPU (works on
+ * HRS_DEVICE_NONE handles), the device call's byte-exact reference: the
+ * locator loop of hrs_heal_host and hrs_heal_erased_host and a host CRC-32
+ * under the same rule (one header compiled by both). stored, crc_out: n
+ * words; verdict: one word; erased_out: parity_size words or NULL; report:
+ * 4 + n words. len == 0: nothing is touched. */
+hrs_status hrs_repair_checked_host(const hrs_codec* codec, uint8_t* const* rows, size_t len, const uint32_t* stored,
+                                   int flags, uint32_t* verdict, int32_t* erased_out, uint32_t* report,
+                                   uint32_t* crc_out);
+
 /* Kernel selection for tests and benchmarks: 0 = auto (default), 1 = force
  * the runtime-matrix bit-sliced kernel, 2 = force the byte-granular kernel,
  * 3 = auto, except that hrs_encode_crc_dev and the heal-with-erasures + CRC

@@ -400,6 +400,34 @@ class HipReedSolomonCode : public HipCode {
       throw std::invalid_argument("healErasedHost: row count does not match the codec");
     check(hrs_heal_erased_host(h_, rows.data(), len, erased.data(), static_cast<int>(erased.size()), report), h_);
   }
+
+  // Checked repair (hrs_repair_checked_dev): scrub + CRC, the stripes whose
+  // checksums differ from stored[nstripes * n] (joinSyndromes: or whose cells
+  // the syndromes blamed) repaired with those cells as erasures, and one
+  // HRS_REPAIR_* verdict per stripe; all arrays on the device, erasedOut
+  // [nstripes * paritySize] may be nullptr. Asynchronous on stream.
+  void repairCheckedDev(const std::vector<uint8_t*>& rows, size_t stride, size_t len, size_t nstripes,
+                        const uint32_t* stored, bool joinSyndromes, uint32_t* verdicts, int32_t* erasedOut,
+                        uint32_t* reports, size_t reportStride, uint32_t* crcOut, void* stream = nullptr) {
+    if (static_cast<int>(rows.size()) != stripeSize() + paritySize())
+      throw std::invalid_argument("repairCheckedDev: row count does not match the codec");
+    check(hrs_repair_checked_dev(h_, rows.data(), stride, len, nstripes, stored,
+                                 joinSyndromes ? HRS_REPAIR_JOIN_SYNDROMES : 0, verdicts, erasedOut, reports,
+                                 reportStride, crcOut, stream), h_);
+  }
+
+  // One stripe of n host rows on the CPU (hrs_repair_checked_host; host-only
+  // handles included): returns the verdict; report holds HRS_SCRUB_HEAD + n
+  // words, stored and crcOut n words, erasedOut paritySize words or nullptr.
+  uint32_t repairCheckedHost(const std::vector<uint8_t*>& rows, size_t len, const uint32_t* stored,
+                             bool joinSyndromes, int32_t* erasedOut, uint32_t* report, uint32_t* crcOut) {
+    if (static_cast<int>(rows.size()) != stripeSize() + paritySize())
+      throw std::invalid_argument("repairCheckedHost: row count does not match the codec");
+    uint32_t verdict = HRS_REPAIR_CLEAN;
+    check(hrs_repair_checked_host(h_, rows.data(), len, stored, joinSyndromes ? HRS_REPAIR_JOIN_SYNDROMES : 0,
+                                  &verdict, erasedOut, report, crcOut), h_);
+    return verdict;
+  }
 };
 
 class HipXORCode : public HipCode {

@@ -49,6 +49,7 @@ EXPORTS = (
     "hrs_scrub_crc_dev", "hrs_heal_crc_dev", "hrs_scrub_batch_host_crc", "hrs_heal_batch_host_crc",
     "hrs_heal_erased_dev", "hrs_heal_erased_host",
     "hrs_heal_erased_crc_dev", "hrs_heal_erased_batch_host", "hrs_heal_erased_batch_host_crc",
+    "hrs_repair_checked_dev", "hrs_repair_checked_host",
 )
 # include/hrs_probe.h, exported by libhrs_probe.so
 PROBE_EXPORTS = ("hrs_probe_stream", "hrs_probe_rows")
@@ -146,6 +147,8 @@ def lib():
         "hrs_heal_erased_crc_dev": ([P, PP, S, S, S, P, I, P, S, P, P, P], I),
         "hrs_heal_erased_batch_host": ([P, P, S, S, S, S, P, I, P, S], I),
         "hrs_heal_erased_batch_host_crc": ([P, P, S, S, S, S, P, I, P, S, P, P], I),
+        "hrs_repair_checked_dev": ([P, PP, S, S, S, P, I, P, P, P, S, P, P], I),
+        "hrs_repair_checked_host": ([P, PP, S, P, I, P, P, P, P], I),
     }
     for name, (args, res) in sigs.items():
         f = getattr(L, name)

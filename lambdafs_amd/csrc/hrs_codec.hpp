@@ -230,6 +230,12 @@ hrs_status run_crc(hrs_codec* c, const uint8_t* const* rows, const size_t* strid
 hrs_status crc_scratch(hrs_codec* c, size_t bytes, hipStream_t s);
 hrs_status crc_scratch_release(hrs_codec* c, hipStream_t s, hrs_status st);
 hrs_status crc_window_tables(hrs_codec* c);  // c->crc_tables_a, uploaded once
+// The fold tables (kCrcLdsWordsB words, device) for rows of `len` bytes cut in
+// windows of `win` bytes, cached per handle; a caller with a fold kernel of its
+// own fetches them before its first launch (a miss uploads them) and calls
+// fold_tables_used after the launch that reads them.
+hrs_status crc_fold_tables(hrs_codec* c, uint64_t len, uint64_t win, hrs_codec::FoldTables** out);
+hrs_status fold_tables_used(hrs_codec* c, hrs_codec::FoldTables* ft, hipStream_t s);
 // run_crc's window pass alone, raw rows laid out for a fold over nrows_total rows.
 hrs_status crc_windows(hrs_codec* c, const uint8_t* const* rows, const size_t* strides, int nrows, int nrows_total,
                        size_t len, size_t nstripes, hipStream_t s, uint32_t* raw);
@@ -331,6 +337,16 @@ hrs_status run_heal_erased_crc(hrs_codec* c, uint8_t* const* rows, size_t stride
                                size_t report_stride, const uint32_t* crc_in, uint32_t* crc_out, hipStream_t s,
                                bool host_memory);
 bool heal_erased_crc_fused_default(bool host_memory);
+
+// ---- checked repair (hrs_scrub_api.cpp, hrs_repair_api.cpp)
+// The argument rules of hrs_repair_checked_dev (with_reports) and
+// hrs_repair_checked_host, in the family's order: scrub_args_ok for a call
+// that writes the rows, the flag bits, then the empty call (*empty = true:
+// return HRS_OK and touch nothing), then stored, verdicts and crc_out not NULL
+// and stored apart from crc_out. The device is the caller's.
+hrs_status repair_args_ok(hrs_codec* c, const uint8_t* const* rows, const uint32_t* reports, size_t report_stride,
+                          size_t len, size_t nstripes, bool with_reports, const uint32_t* stored, int flags,
+                          const uint32_t* verdicts, const uint32_t* crc_out, bool* empty);
 
 // ---- per-call device tables (hrs_batch_api.cpp)
 // The next of the handle's two batch slots (pinned staging `host` + device

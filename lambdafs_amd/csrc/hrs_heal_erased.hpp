@@ -34,4 +34,21 @@ struct HealErasedArgs {
 hipError_t launch_heal_erased(const HealErasedArgs& a, hipStream_t s);
 hipError_t launch_heal_erased_bytewise(const HealErasedArgs& a, hipStream_t s);
 
+// The listed form (checked repair, hrs_repair.hpp): the same two kernels over
+// the stripes a device list names. list[0] = how many, read at kernel entry
+// and clamped to nstripes; list[1 + i] = the i-th listed stripe, whose pattern
+// is h.pats[that stripe] (h.pat is not read). An entry >= nstripes is skipped,
+// never indexed with. h.s.ntasks is the upper bound nstripes * nwin (bytewise:
+// nstripes * (len - col0)) the grid is sized for; blocks past count * nwin
+// leave before they load anything.
+struct HealListedArgs {
+  HealErasedArgs h;
+  const uint32_t* list;
+  uint32_t nstripes;
+  uint32_t pad_;
+};
+
+hipError_t launch_heal_listed(const HealListedArgs& a, hipStream_t s);
+hipError_t launch_heal_listed_bytewise(const HealListedArgs& a, hipStream_t s);
+
 }  // namespace hrs

@@ -6,9 +6,11 @@
 // patterns: validated, de-duplicated, with the constants the kernels of
 // hrs_heal_erased.hip and hrs_heal_erased_crc.hip multiply by) and one stripe
 // healed on the CPU (hrs_heal_host, hrs_heal_erased_host), the kernels'
-// byte-exact reference. The host-memory
-// batches are in hrs_batch_api.cpp beside the pipeline they share. The
-// per-column algorithm is hrs_locator.hpp, the same code the kernels run.
+// byte-exact reference; also hrs_repair_checked_host, checked repair of one
+// stripe over those same CPU pieces (its device call is hrs_repair_api.cpp).
+// The host-memory batches are in hrs_batch_api.cpp beside the pipeline they
+// share. The per-column algorithm is hrs_locator.hpp, the same code the
+// kernels run.
 //
 // The entry points share one argument gate (scrub_args_ok), the device calls
 // one window / tail launcher (run_windows_tail) and the CPU calls one column
@@ -29,6 +31,7 @@
 #include "hrs_internal.hpp"
 #include "hrs_launch.hpp"
 #include "hrs_locator.hpp"
+#include "hrs_repair_rule.hpp"
 
 namespace hrs::api {
 
@@ -147,9 +150,11 @@ namespace {
 
 // One stripe on the CPU: the column loop of hrs_heal_host (an empty pattern,
 // locate() on the column's syndromes) and hrs_heal_erased_host (the erased
-// cells count as zero and are rebuilt, locate_errata()).
+// cells count as zero and are rebuilt, locate_errata()). write = false (empty
+// pattern only) is the scrub: the same report with nothing stored and word 3
+// left at 0, pass 1 of hrs_repair_checked_host.
 template <int P>
-void heal_stripe(int n, uint8_t* const* rows, size_t len, const hrs::ErasePattern& pt, uint32_t* rep) {
+void heal_stripe(int n, uint8_t* const* rows, size_t len, const hrs::ErasePattern& pt, uint32_t* rep, bool write) {
   const hrs::locator::Field& f = kHostField;
   const int e = pt.e;
   for (size_t col = 0; col < len; ++col) {
@@ -178,7 +183,7 @@ void heal_stripe(int n, uint8_t* const* rows, size_t len, const hrs::ErasePatter
     }
     for (int j = 0; j < nloc; ++j) {
       ++rep[HRS_SCRUB_HEAD + loc[j]];
-      if (u[j] == 0) continue;  // a blamed location whose value stands: nothing to store
+      if (u[j] == 0 || !write) continue;  // a blamed location whose value stands: nothing to store
       rows[loc[j]][col] ^= u[j];
       ++rep[HRS_SCRUB_PATCHED];
     }
@@ -186,11 +191,27 @@ void heal_stripe(int n, uint8_t* const* rows, size_t len, const hrs::ErasePatter
 }
 
 // hrs_heal_host and hrs_heal_erased_host after their argument checks.
-hrs_status heal_host(hrs_codec* c, uint8_t* const* rows, size_t len, const hrs::ErasePattern& pt, uint32_t* report) {
+hrs_status heal_host(hrs_codec* c, uint8_t* const* rows, size_t len, const hrs::ErasePattern& pt, uint32_t* report,
+                     bool write = true) {
   if (len == 0) return HRS_OK;
   for (int e = 0; e < HRS_SCRUB_HEAD + c->n; ++e) report[e] = e == HRS_SCRUB_FIRST_BAD ? HRS_SCRUB_NONE : 0u;
-  (void)hrs::dispatch_p<1, 8>(c->p, [&](auto P) { heal_stripe<P>(c->n, rows, len, pt, report); });
+  (void)hrs::dispatch_p<1, 8>(c->p, [&](auto P) { heal_stripe<P>(c->n, rows, len, pt, report, write); });
   return HRS_OK;
+}
+
+// CRC-32 (crc32.hpp) of one host cell, slicing by 4.
+uint32_t host_crc32(const uint8_t* p, size_t len) {
+  static const hrs::crc::Slice4 sl = hrs::crc::make_slice4();
+  uint32_t c = 0xFFFFFFFFu;
+  size_t i = 0;
+  for (; i + 4 <= len; i += 4) {
+    uint32_t w;
+    std::memcpy(&w, p + i, 4);
+    c ^= w;
+    c = sl.s[3].t[c & 0xFFu] ^ sl.s[2].t[(c >> 8) & 0xFFu] ^ sl.s[1].t[(c >> 16) & 0xFFu] ^ sl.s[0].t[c >> 24];
+  }
+  for (; i < len; ++i) c = sl.s[0].t[(c ^ p[i]) & 0xFFu] ^ (c >> 8);
+  return c ^ 0xFFFFFFFFu;
 }
 
 }  // namespace
@@ -311,29 +332,11 @@ hrs_status erased_key(hrs_codec* c, const int* erased, int cap, size_t stripe, s
 
 // The device table entry of an erased set (hrs_heal_erased.hpp).
 hrs::ErasePattern make_pattern(int p, const std::vector<int>& key) {
-  const hrs::locator::Field& f = kHostField;
   hrs::ErasePattern pt{};
-  const int e = static_cast<int>(key.size()), pp = p - e;
-  pt.e = e;
-  for (int m = 0; m < e; ++m) {
-    pt.loc[m] = static_cast<uint8_t>(key[m]);
-    pt.mask[key[m] >> 5] |= 1u << (key[m] & 31);
-  }
-  while ((pt.mask[pt.spare >> 5] >> (pt.spare & 31)) & 1u) ++pt.spare;
-  hrs::locator::erasure_locator(f, e, pt.loc, pt.gamma);
-  uint8_t mat[hrs::locator::kMaxSyndromes][hrs::locator::kMaxSyndromes] = {};
-  for (int o = 0; o < pp; ++o)
-    for (int j = 0; j <= e; ++j) mat[o][o + e - j] = pt.gamma[j];
-  if (e > 0) {
-    std::vector<uint8_t> v(static_cast<size_t>(e) * e);  // v[i][m] = alpha^(loc[m] i)
-    for (int i = 0; i < e; ++i)
-      for (int m = 0; m < e; ++m) v[static_cast<size_t>(i) * e + m] = hrs::gf::alpha_pow(static_cast<long>(key[m]) * i);
-    gf_invert(v, e);  // distinct locations: never singular
-    for (int m = 0; m < e; ++m)
-      for (int i = 0; i < e; ++i) mat[pp + m][i] = v[static_cast<size_t>(m) * e + i];
-  }
-  for (int i = 0; i < p; ++i)
-    for (int o = 0; o < p; ++o) pt.cw[i] |= static_cast<uint64_t>(mat[o][i]) << (8 * o);
+  pt.e = static_cast<int>(key.size());
+  for (int m = 0; m < pt.e; ++m) pt.loc[m] = static_cast<uint8_t>(key[m]);
+  hrs::repair::PatternWork work;
+  hrs::repair::fill_pattern(kHostField, p, pt, work);  // the code repair_plan_kernel runs (hrs_repair.hip)
   return pt;
 }
 
@@ -508,6 +511,27 @@ hrs_status heal_erased_dev_entry(hrs_codec* c, uint8_t* const* rows, size_t stri
 
 }  // namespace
 
+// ---- checked repair (the device call is hrs_repair_api.cpp)
+
+hrs_status repair_args_ok(hrs_codec* c, const uint8_t* const* rows, const uint32_t* reports, size_t report_stride,
+                          size_t len, size_t nstripes, bool with_reports, const uint32_t* stored, int flags,
+                          const uint32_t* verdicts, const uint32_t* crc_out, bool* empty) {
+  *empty = false;
+  const hrs_status st = scrub_args_ok(c, rows, reports, report_stride, len, nstripes,
+                                      (with_reports ? kScrubWithReports : 0u) | kScrubRowsWritten);
+  if (st != HRS_OK) return st;
+  if (flags & ~HRS_REPAIR_JOIN_SYNDROMES) return fail(c, HRS_EINVAL, "flags %#x: only HRS_REPAIR_JOIN_SYNDROMES is defined", flags);
+  if (len == 0 || nstripes == 0) {
+    *empty = true;
+    return HRS_OK;
+  }
+  if (!stored || !verdicts || !crc_out)
+    return fail(c, HRS_EINVAL, "%s is NULL", !stored ? "stored" : !verdicts ? (with_reports ? "verdicts" : "verdict") : "crc_out");
+  if (stored == crc_out || !crc_arrays_apart(stored, crc_out, nstripes * static_cast<size_t>(c->n)))
+    return fail(c, HRS_EINVAL, "stored and crc_out overlap");
+  return HRS_OK;
+}
+
 }  // namespace hrs::api
 
 using namespace hrs::api;
@@ -596,6 +620,44 @@ hrs_status hrs_heal_erased_host(const hrs_codec* cc, uint8_t* const* rows, size_
   st = erased_key(c, erased, num_erased, 0, key);
   if (st != HRS_OK) return st;
   return heal_host(c, rows, len, make_pattern(c->p, key), report);
+}
+
+hrs_status hrs_repair_checked_host(const hrs_codec* cc, uint8_t* const* rows, size_t len, const uint32_t* stored,
+                                   int flags, uint32_t* verdict, int32_t* erased_out, uint32_t* report,
+                                   uint32_t* crc_out) {
+  namespace rp = hrs::repair;
+  auto* c = const_cast<hrs_codec*>(cc);
+  bool empty = false;
+  const hrs_status st = repair_args_ok(c, rows, report, 0, len, 1, false, stored, flags, verdict, crc_out, &empty);
+  if (st != HRS_OK || empty) return st;
+  const int n = c->n, p = c->p;
+  // pass 1: the cells' CRCs and the scrub's report, nothing stored
+  for (int l = 0; l < n; ++l) crc_out[l] = host_crc32(rows[l], len);
+  (void)heal_host(c, rows, len, hrs::ErasePattern{}, report, false);
+  int nd = 0;
+  std::vector<int> key;
+  for (int l = 0; l < n; ++l) {
+    nd += rp::doubted(crc_out[l], stored[l]) ? 1 : 0;
+    if (rp::suspected(crc_out[l], stored[l], report[HRS_SCRUB_HEAD + l], flags)) key.push_back(l);
+  }
+  if (erased_out)
+    for (int m = 0; m < p; ++m) erased_out[m] = -1;
+  *verdict = rp::plan_verdict(nd, static_cast<int>(key.size()), p, report[HRS_SCRUB_BAD], report[HRS_SCRUB_UNRESOLVED]);
+  if (*verdict != rp::kListed) return HRS_OK;
+  if (erased_out)
+    for (size_t m = 0; m < key.size(); ++m) erased_out[m] = key[m];
+  // pass 2: the heal with the erased set B, then the CRCs of the cells as it leaves them
+  (void)heal_host(c, rows, len, make_pattern(p, key), report);
+  bool any_f = false, any_fd = false;
+  for (int l = 0; l < n; ++l) {
+    const uint32_t now = host_crc32(rows[l], len);
+    const bool in_f = rp::doubted(now, stored[l]);
+    any_f |= in_f;
+    any_fd |= in_f && rp::doubted(crc_out[l], stored[l]);
+    crc_out[l] = now;
+  }
+  *verdict = rp::final_verdict(any_f, any_fd, report[HRS_SCRUB_UNRESOLVED]);
+  return HRS_OK;
 }
 
 }  // extern "C"

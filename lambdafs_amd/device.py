@@ -783,6 +783,88 @@ def checksums_to_erased(crcs, stored, p, reports=None):
     return erased
 
 
+# hrs_repair_checked_dev / hrs_repair_checked_host: verdicts and the flag
+REPAIR_CLEAN, REPAIR_REPAIRED, REPAIR_RESTAMP, REPAIR_FAILED, REPAIR_TOOMANY, REPAIR_AMBIGUOUS = range(6)
+REPAIR_JOIN_SYNDROMES = 1
+
+
+def _repair_checked(code, rows, stride, L, S, ref, stored, join_syndromes):
+    torch = _lib.torch
+    n, p = code.stripeSize() + code.paritySize(), code.paritySize()
+    if (not isinstance(stored, torch.Tensor) or stored.shape != (S, n) or stored.dtype != torch.int32
+            or not stored.is_contiguous() or stored.device != ref.device):
+        raise ValueError(f"stored must be a contiguous int32 device tensor [S, {n}]")
+    verdicts = torch.empty((S,), dtype=torch.int32, device=ref.device)
+    erased = torch.empty((S, p), dtype=torch.int32, device=ref.device)
+    reports = torch.empty((S, SCRUB_HEAD + n), dtype=torch.int32, device=ref.device)
+    crcs = torch.empty((S, n), dtype=torch.int32, device=ref.device)
+    if L == 0 or S == 0:  # the call touches nothing: every stripe is clean, every CRC is over no bytes
+        verdicts.zero_()
+        erased.fill_(-1)
+        reports.zero_()
+        reports[:, SCRUB_FIRST_BAD] = -1
+        crcs.zero_()
+    code._check(_lib.lib().hrs_repair_checked_dev(
+        code._handle(), rows, stride, L, S, stored.data_ptr(), REPAIR_JOIN_SYNDROMES if join_syndromes else 0,
+        verdicts.data_ptr(), erased.data_ptr(), reports.data_ptr(), SCRUB_HEAD + n, crcs.data_ptr(), _stream(ref)))
+    return verdicts, erased, reports, crcs
+
+
+def repair_checked_stripes(code, stripes, stored, join_syndromes=False):
+    """Checked repair (hrs_repair_checked_dev) over stripes[S, n, L], all on the
+    device and on the current stream: the cells' CRC-32s are compared with the
+    checksums `stored` ([S, n] int32, hops order); a stripe whose checksums all
+    match and whose syndromes are clean is REPAIR_CLEAN; one with more than p
+    doubted cells is REPAIR_TOOMANY, one with unresolved columns and no
+    differing checksum REPAIR_AMBIGUOUS, and neither is written; every other
+    stripe is healed in place with the doubted cells as erasures
+    (heal_erased_stripes' bytes and report) and called REPAIR_REPAIRED when
+    every CRC then equals the stored one, REPAIR_RESTAMP when the stripe is a
+    codeword and only checksums that matched before now differ (stale cells
+    stamped with their own checksum: take the new values from crcs), else
+    REPAIR_FAILED. join_syndromes adds the cells pass 1's syndromes blamed to
+    the doubted ones (checksums_to_erased with reports): for few-column damage;
+    whole-cell garbage makes the locator blame sound cells. Returns device
+    tensors (verdicts [S], erased [S, p] ascending and -1 padded, reports
+    [S, 4 + n], crcs [S, n]), all int32."""
+    n = code.stripeSize() + code.paritySize()
+    if stripes.dim() != 3 or stripes.shape[1] != n:
+        raise ValueError(f"stripes must be [S, {n}, L]")
+    rows, stride, L, S = _stripe_rows(stripes, range(n))
+    return _repair_checked(code, rows, stride, L, S, stripes, stored, join_syndromes)
+
+
+def repair_checked_rows(code, row_views, stored, join_syndromes=False):
+    """repair_checked_stripes with explicit [S, L] row views, one per location in hops order."""
+    n = code.stripeSize() + code.paritySize()
+    if len(row_views) != n or any(v is None for v in row_views):
+        raise ValueError(f"need {n} row views")
+    rows, stride, L, S = _rows(row_views)
+    return _repair_checked(code, rows, stride, L, S, row_views[0], stored, join_syndromes)
+
+
+def repair_checked_host(code, rows, stored, join_syndromes=False):
+    """hrs_repair_checked_host: repair_checked_stripes for one stripe of n HOST
+    rows (as for heal_host) on the CPU, the device call's byte-exact reference;
+    works on host-only handles. stored: n uint32 checksums. Returns (verdict,
+    erased int32 [p], report uint32 [4 + n], crcs uint32 [n])."""
+    n, p = code.stripeSize() + code.paritySize(), code.paritySize()
+    L = _host_stripe_rows(rows, n)
+    st = np.ascontiguousarray(np.asarray(stored).astype(np.int64) & 0xFFFFFFFF, dtype=np.uint32)
+    if st.shape != (n,):
+        raise ValueError(f"stored must hold {n} checksums")
+    verdict = np.zeros(1, dtype=np.uint32)
+    erased = np.full(p, -1, dtype=np.int32)
+    report = np.zeros(SCRUB_HEAD + n, dtype=np.uint32)
+    report[SCRUB_FIRST_BAD] = SCRUB_NONE
+    crcs = np.zeros(n, dtype=np.uint32)
+    code._check(_lib.lib().hrs_repair_checked_host(
+        code._handle(), _lib.ptr_array([r.ctypes.data for r in rows]), L, st.ctypes.data,
+        REPAIR_JOIN_SYNDROMES if join_syndromes else 0, verdict.ctypes.data, erased.ctypes.data, report.ctypes.data,
+        crcs.ctypes.data))
+    return int(verdict[0]), erased, report, crcs
+
+
 PROBE_COPY, PROBE_READ, PROBE_WRITE = 0, 1, 2
 WAVE_TASKS, GRID_STRIDE, BLOCK_RANGE = 0, 1, 2  # hrs_probe_stream schedules
 
