@@ -32,7 +32,7 @@
 namespace hrs {
 namespace {
 
-// zmul / slice4 / lane_tree: hrs_device.hpp
+// zmul / slice4 / lane_tree / crc_window_raw / fold_row: hrs_device.hpp
 
 template <bool ALIGNED>
 __global__ void __launch_bounds__(kCrcBlockThreads) crc_window_kernel(const CrcWinArgs a) {
@@ -54,48 +54,7 @@ __global__ void __launch_bounds__(kCrcBlockThreads) crc_window_kernel(const CrcW
     const uint64_t stripe = sr / a.nrows;
     const int row = static_cast<int>(sr - stripe * a.nrows);
     const uint8_t* base = a.rows[row] + stripe * a.stride[row];
-    // the window covers [end - kCrcWindow, end); bytes below lo read as zero
-    const bool full = w < a.nwin;
-    const int64_t end = full ? static_cast<int64_t>((w + 1) * kCrcWindow) : static_cast<int64_t>(a.len);
-    const int64_t lo = full ? static_cast<int64_t>(w * kCrcWindow) : static_cast<int64_t>(a.nwin * kCrcWindow);
-    const int64_t start = end - kCrcWindow + lane * crc::kPieceBytes;
-    uint32_t c = 0;
-#pragma unroll 1
-    for (int g = 0; g < crc::kPieces; g += kCrcGroup) {
-      uint32_t words[kCrcGroup][4];
-#pragma unroll
-      for (int q = 0; q < kCrcGroup; ++q) {
-        const int64_t pos0 = start + static_cast<int64_t>(g + q) * crc::kChunkBytes;
-        if (ALIGNED && full) {
-          const u32x4 v = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(base + pos0));
-          words[q][0] = v[0];
-          words[q][1] = v[1];
-          words[q][2] = v[2];
-          words[q][3] = v[3];
-        } else {
-#pragma unroll
-          for (int j = 0; j < 4; ++j) {
-            uint32_t x = 0;
-#pragma unroll
-            for (int b = 0; b < 4; ++b) {
-              const int64_t pos = pos0 + 4 * j + b;
-              if (pos >= lo) x |= static_cast<uint32_t>(base[pos]) << (8 * b);
-            }
-            words[q][j] = x;
-          }
-        }
-      }
-      uint32_t ch[kCrcGroup];
-#pragma unroll
-      for (int q = 0; q < kCrcGroup; ++q) ch[q] = 0u;
-#pragma unroll
-      for (int st = 0; st < 4; ++st)
-#pragma unroll
-        for (int q = 0; q < kCrcGroup; ++q) ch[q] = slice4(slices, ch[q] ^ words[q][st]);
-#pragma unroll
-      for (int q = 0; q < kCrcGroup; ++q) c = (g + q == 0) ? ch[q] : (zmul(zchunk, c) ^ ch[q]);
-    }
-    c = lane_tree(tree, c);
+    const uint32_t c = crc_window_raw<ALIGNED>(base, w, a.nwin, a.len, lane, slices, zchunk, tree);
     if (lane == 0) a.raw[(stripe * a.nrows_total + a.row0 + row) * wpr + w] = c;
   }
 }
@@ -113,15 +72,8 @@ __global__ void __launch_bounds__(256) crc_fold_kernel(const CrcFoldArgs a) {
   const uint64_t pad = static_cast<uint64_t>(a.G) * 64 - a.nwin;
   const uint32_t nwaves = gridDim.x * (blockDim.x / 64);
   for (uint64_t sr = wave_id_in_grid(); sr < a.nsr; sr += nwaves) {
-    const uint32_t* raw = a.raw + sr * wpr;
-    uint32_t c = 0;
-    for (int g = 0; g < a.G; ++g) {
-      const int64_t w = static_cast<int64_t>(lane) * a.G + g - static_cast<int64_t>(pad);
-      if (w >= 0) c = zmul(zw, c) ^ raw[w];
-    }
-    c = lane_tree(ztree, c);
+    const uint32_t c = fold_row(a.raw + sr * wpr, a.nwin, a.G, pad, a.tail, zw, ztree, ztail, lane);
     if (lane == 0) {
-      if (a.tail) c = zmul(ztail, c) ^ raw[a.nwin];
       const uint32_t state = (a.crc_in ? a.crc_in[sr] : 0u) ^ 0xFFFFFFFFu;
       a.crc_out[sr] = zmul(zlen, state) ^ c ^ 0xFFFFFFFFu;
     }

@@ -369,6 +369,77 @@ __device__ __forceinline__ uint32_t lane_tree(const uint32_t* tree, uint32_t c) 
   return c;
 }
 
+// The raw CRC (in lane 0) of window w of the len-byte row at `base`, of which
+// nwin windows are full: 32 chunks of 1 KiB, lane l on the 16-byte piece at
+// 16 l of every chunk, kCrcGroup chunks loaded and chained together, the
+// lane's pieces joined in chunk order with Z_1024 (zchunk), the lanes by the
+// tree. The row tail (w == nwin) is a right-aligned window whose leading bytes
+// read as zero. ALIGNED: a full window's pieces are 16-byte loads.
+template <bool ALIGNED>
+__device__ __forceinline__ uint32_t crc_window_raw(const uint8_t* base, uint64_t w, uint64_t nwin, uint64_t len,
+                                                   int lane, const SliceTab& slices, const uint32_t* zchunk,
+                                                   const uint32_t* tree) {
+  // the window covers [end - kCrcWindow, end); bytes below lo read as zero
+  const bool full = w < nwin;
+  const int64_t end = full ? static_cast<int64_t>((w + 1) * kCrcWindow) : static_cast<int64_t>(len);
+  const int64_t lo = full ? static_cast<int64_t>(w * kCrcWindow) : static_cast<int64_t>(nwin * kCrcWindow);
+  const int64_t start = end - kCrcWindow + lane * crc::kPieceBytes;
+  uint32_t c = 0;
+#pragma unroll 1
+  for (int g = 0; g < crc::kPieces; g += kCrcGroup) {
+    uint32_t words[kCrcGroup][4];
+#pragma unroll
+    for (int q = 0; q < kCrcGroup; ++q) {
+      const int64_t pos0 = start + static_cast<int64_t>(g + q) * crc::kChunkBytes;
+      if (ALIGNED && full) {
+        const u32x4 v = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(base + pos0));
+        words[q][0] = v[0];
+        words[q][1] = v[1];
+        words[q][2] = v[2];
+        words[q][3] = v[3];
+      } else {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          uint32_t x = 0;
+#pragma unroll
+          for (int b = 0; b < 4; ++b) {
+            const int64_t pos = pos0 + 4 * j + b;
+            if (pos >= lo) x |= static_cast<uint32_t>(base[pos]) << (8 * b);
+          }
+          words[q][j] = x;
+        }
+      }
+    }
+    uint32_t ch[kCrcGroup];
+#pragma unroll
+    for (int q = 0; q < kCrcGroup; ++q) ch[q] = 0u;
+#pragma unroll
+    for (int st = 0; st < 4; ++st)
+#pragma unroll
+      for (int q = 0; q < kCrcGroup; ++q) ch[q] = slice4(slices, ch[q] ^ words[q][st]);
+#pragma unroll
+    for (int q = 0; q < kCrcGroup; ++q) c = (g + q == 0) ? ch[q] : (zmul(zchunk, c) ^ ch[q]);
+  }
+  return lane_tree(tree, c);
+}
+
+// The raw CRC (in lane 0) of a row from its windows' raw CRCs raw[0..nwin]:
+// G full windows per lane joined with Z_window (zw), the first `pad` = 64 G -
+// nwin places empty, a lane tree with Z_{window*G*2^t} (ztree), then the tail
+// window raw[nwin], if the row has one, joined with Z_tail.
+__device__ __forceinline__ uint32_t fold_row(const uint32_t* raw, uint64_t nwin, int G, uint64_t pad, uint64_t tail,
+                                             const uint32_t* zw, const uint32_t* ztree, const uint32_t* ztail,
+                                             int lane) {
+  uint32_t c = 0;
+  for (int g = 0; g < G; ++g) {
+    const int64_t w = static_cast<int64_t>(lane) * G + g - static_cast<int64_t>(pad);
+    if (w >= 0) c = zmul(zw, c) ^ raw[w];
+  }
+  c = lane_tree(ztree, c);
+  if (lane == 0 && tail) c = zmul(ztail, c) ^ raw[nwin];
+  return c;
+}
+
 // Lane l receives v of lane l + N within its row of 16 lanes (0 past the
 // row's end): one DPP row_shl move on the VALU instead of a ds_bpermute
 // through the LDS unit.

@@ -15,90 +15,117 @@
 // locator::locate_errata on it, patches the survivors byte by byte as the
 // heal does and replaces the column's erased bytes in its registers before
 // the row stores, so each byte is stored once, by the lane that owns it.
+//
+// Each walk has one body (heal_window, heal_one_column; the tail from tv = M S
+// on is heal_tail of hrs_heal_erased_device.hpp, shared with the fused CRC
+// form) and two kernels that call it: over every stripe of a batch, and over
+// the stripes a device list names.
 #include <hip/hip_runtime.h>
 
 #include "hrs_device.hpp"
 #include "hrs_heal_erased.hpp"
+#include "hrs_heal_erased_device.hpp"
 #include "hrs_launch.hpp"
 #include "hrs_locator.hpp"
+#include "hrs_scrub_device.hpp"
 
 namespace hrs {
 namespace {
 
-__constant__ gf::Tables d_erased_tables = gf::make_tables();
-
 constexpr int kErasedGroup = 8;  // rows of a window in flight per wave; groups are aligned, one mask byte each
+constexpr int kHistWords = kScrubHead + kScrubMaxRows;  // per wave
+
+// The block's prologue keeps this unit's own text, not load_field_tables and
+// hist_init of hrs_scrub_device.hpp: with those the compiler allocates the
+// window kernels' registers differently (heal_erased_kernel<1> 111 -> 96
+// VGPRs, <3> 134 -> 112), code the batch calls were not measured with.
+__constant__ gf::Tables d_erased_tables = gf::make_tables();
 
 __device__ __forceinline__ void load_tables(uint8_t* s_exp, uint8_t* s_log) {
   for (int i = threadIdx.x; i < 512; i += blockDim.x) s_exp[i] = d_erased_tables.exp[i];
   for (int i = threadIdx.x; i < 256; i += blockDim.x) s_log[i] = d_erased_tables.log[i];
 }
 
-// One column (survivor syndromes s) of a stripe with pattern pt: runs the
-// locator, patches the blamed survivors at rows[loc] + at, adds the column to
-// the counters at h (a per-wave LDS histogram or the stripe's report) and
-// leaves the erased values in v. Returns whether the column was bad.
-template <int P>
-__device__ __forceinline__ bool heal_column(const locator::Field& f, int n, const uint8_t (&s)[P],
-                                            const ErasePattern& pt, uint32_t col, uint32_t* h,
-                                            const uint8_t* const* rows, uint64_t at,
-                                            uint8_t (&v)[locator::kMaxErased]) {
-  int nloc = 0;
-  uint8_t loc[locator::kMaxErrors], u[locator::kMaxErrors];
-  const int state = locator::locate_errata<P>(f, n, s, pt.e, pt.loc, pt.gamma, &nloc, loc, u, v);
-  if (state == locator::kConsistent) return false;
-  atomicAdd(&h[0], 1u);
-  atomicMin(&h[2], col);
-  if (state == locator::kUnresolved) {
-    atomicAdd(&h[1], 1u);
-    return true;
+// Every wave's histogram at rest: a report's layout, word 2 is a minimum.
+__device__ __forceinline__ void init_hist(uint32_t (&s_hist)[kWavesPerBlock][kHistWords]) {
+  for (int i = threadIdx.x; i < kWavesPerBlock * kHistWords; i += blockDim.x) {
+    const int e = i % kHistWords;
+    s_hist[i / kHistWords][e] = e == 2 ? kScrubNone : 0u;
   }
-  uint32_t patched = 0u;
-  for (int j = 0; j < nloc; ++j) {
-    atomicAdd(&h[kScrubHead + loc[j]], 1u);
-    if (u[j] != 0) {
-      uint8_t* q = const_cast<uint8_t*>(rows[loc[j]]) + at;
-      *q = static_cast<uint8_t>(*q ^ u[j]);
-      ++patched;
+}
+
+// ------------------------------------------------------ vector kernels
+
+// One window: the 2 KiB at `off` of the rows of `stripe` (base = stripe *
+// stride + off), whose pattern the wave holds in pv. pat_index() is the
+// pattern's index in the table; it is called for a bad column only.
+template <int P, class PatIndex>
+__device__ __forceinline__ void heal_window(const HealErasedArgs& ha, const locator::Field& f, uint32_t pv,
+                                            uint64_t stripe, uint64_t off, uint64_t base, int lane, uint32_t* hist,
+                                            int nwords, PatIndex&& pat_index) {
+  const ScrubArgs& a = ha.s;
+  const int spare = static_cast<int>(pattern_word(pv, kPatSpare));
+  uint32_t acc[P][8];
+#pragma unroll
+  for (int i = 0; i < P; ++i)
+#pragma unroll
+    for (int q = 0; q < 8; ++q) acc[i][q] = 0u;
+  for (int l0 = (a.n - 1) & ~(kErasedGroup - 1); l0 >= 0; l0 -= kErasedGroup) {
+    // locations l0 + 7 .. l0; bit g of `gone`: l0 + g is erased
+    const uint32_t gone = (pattern_word(pv, kPatMask + (l0 >> 5)) >> (l0 & 31)) & ((1u << kErasedGroup) - 1u);
+    uint32_t w[kErasedGroup][8];
+    // Every slot loads, in one straight run, so that the loads of a group are
+    // in flight together (a load behind a branch of its own waits for the
+    // ones before it). A slot with no survivor row (erased, or past n - 1)
+    // reads one 16-byte piece of a survivor's window in every lane instead:
+    // one cache line, never an erased cell, and the result is not used.
+#pragma unroll
+    for (int g = kErasedGroup - 1; g >= 0; --g) {
+      const bool take = l0 + g < a.n && !((gone >> g) & 1u);
+      const uint8_t* p = a.rows[take ? l0 + g : spare] + base;
+      const uint32_t lo = take ? lane * 16u : 0u, hi = take ? 1024u : 0u;
+      const u32x4 x = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(p + lo));
+      const u32x4 y = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(p + lo + hi));
+      w[g][0] = x[0]; w[g][1] = x[1]; w[g][2] = x[2]; w[g][3] = x[3];
+      w[g][4] = y[0]; w[g][5] = y[1]; w[g][6] = y[2]; w[g][7] = y[3];
     }
+#pragma unroll
+    for (int g = kErasedGroup - 1; g >= 0; --g)
+      if (l0 + g < a.n) {
+        const bool live = !((gone >> g) & 1u);
+        if (live) bitslice(w[g]);
+#pragma unroll
+        for (int i = 0; i < P; ++i) {
+#pragma unroll
+          for (int r = 0; r < i; ++r) xtime(acc[i]);
+          if (live) {
+#pragma unroll
+            for (int q = 0; q < 8; ++q) acc[i][q] ^= w[g][q];
+          }
+        }
+      }
   }
-  if (patched != 0u) atomicAdd(&h[kScrubPatched], patched);
-  return true;
-}
-
-// ------------------------------------------------------ vector kernel
-
-// The calling wave's copy of its stripe's pattern: lane j % 32 holds dword j
-// of the 128-byte table entry (one coalesced load per window); a field comes
-// out by v_readlane into an SGPR, so the tests on it run on the scalar unit.
-constexpr int kPatE = offsetof(ErasePattern, e) / 4, kPatMask = offsetof(ErasePattern, mask) / 4,
-              kPatCw = offsetof(ErasePattern, cw) / 4, kPatLoc = offsetof(ErasePattern, loc) / 4, kPatSpare = offsetof(ErasePattern, spare) / 4;
-static_assert(sizeof(ErasePattern) == 128 && offsetof(ErasePattern, cw) % 8 == 0, "one dword per lane of a half wave");
-
-__device__ __forceinline__ uint32_t load_pattern(const HealErasedArgs& ha, int32_t index, int lane) {
-  return reinterpret_cast<const uint32_t*>(ha.pats + index)[lane & 31];
-}
-
-__device__ __forceinline__ uint32_t pattern_word(uint32_t pv, int word) {
-  return static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(pv), word));
+  const bool dirty = heal_tail<P>(f, a.n, a.rows, ha.pats, pv, stripe * a.stride, static_cast<uint32_t>(off), lane,
+                                  hist, acc, pat_index, [&](int l, const uint32_t(&row)[8], bool) {
+                                    store_row(const_cast<uint8_t*>(a.rows[l]) + base, lane, row);
+                                  });
+  // this window's counts to its stripe
+  if (dirty) hist_flush(hist, a.reports + stripe * a.report_stride, nwords, lane);
 }
 
 template <int P>
 __global__ void __launch_bounds__(kBlockThreads) heal_erased_kernel(const HealErasedArgs ha) {
   __shared__ uint8_t s_exp[512];
   __shared__ uint8_t s_log[256];
-  __shared__ uint32_t s_hist[kWavesPerBlock][kScrubHead + kScrubMaxRows];
+  __shared__ uint32_t s_hist[kWavesPerBlock][kHistWords];
   const ScrubArgs& a = ha.s;
   load_tables(s_exp, s_log);
-  const int nwords = kScrubHead + a.n;
-  for (int i = threadIdx.x; i < kWavesPerBlock * (kScrubHead + kScrubMaxRows); i += blockDim.x) {
-    const int e = i % (kScrubHead + kScrubMaxRows);
-    s_hist[i / (kScrubHead + kScrubMaxRows)][e] = e == 2 ? kScrubNone : 0u;
-  }
+  init_hist(s_hist);
   __syncthreads();
   const locator::Field f{s_exp, s_log};
   const int lane = threadIdx.x & 63;
   uint32_t* hist = s_hist[threadIdx.x >> 6];
+  const int nwords = kScrubHead + a.n;
   const WaveTasks wt = wave_tasks(a.ntasks, a.order);
   // Two loads lead to a window's pattern (its stripe's index, then the table
   // entry); both run ahead of the windows so that neither is waited for: while
@@ -109,7 +136,7 @@ __global__ void __launch_bounds__(kBlockThreads) heal_erased_kernel(const HealEr
   int32_t pi_next = 0;
   if (wt.at(0) < wt.end) {
     stripe_cur = wt.at(0) / a.nwin;
-    pv_next = load_pattern(ha, ha.pat[stripe_cur], lane);
+    pv_next = load_pattern(ha.pats, ha.pat[stripe_cur], lane);
   }
   if (wt.at(1) < wt.end) {
     stripe_next = wt.at(1) / a.nwin;
@@ -123,171 +150,37 @@ __global__ void __launch_bounds__(kBlockThreads) heal_erased_kernel(const HealEr
     const uint64_t base = stripe * a.stride + off;
     const uint32_t pv = pv_next;
     stripe_cur = stripe_next;
-    if (wt.at(j + 1) < wt.end) pv_next = load_pattern(ha, pi_next, lane);
+    if (wt.at(j + 1) < wt.end) pv_next = load_pattern(ha.pats, pi_next, lane);
     if (wt.at(j + 2) < wt.end) {
       stripe_next = wt.at(j + 2) / a.nwin;
       pi_next = ha.pat[stripe_next];
     }
-    const int pp = P - static_cast<int>(pattern_word(pv, kPatE));  // wave-uniform, like every field
-    const int spare = static_cast<int>(pattern_word(pv, kPatSpare));
-    uint32_t acc[P][8];
-#pragma unroll
-    for (int i = 0; i < P; ++i)
-#pragma unroll
-      for (int q = 0; q < 8; ++q) acc[i][q] = 0u;
-    for (int l0 = (a.n - 1) & ~(kErasedGroup - 1); l0 >= 0; l0 -= kErasedGroup) {
-      // locations l0 + 7 .. l0; bit g of `gone`: l0 + g is erased
-      const uint32_t gone = (pattern_word(pv, kPatMask + (l0 >> 5)) >> (l0 & 31)) & ((1u << kErasedGroup) - 1u);
-      uint32_t w[kErasedGroup][8];
-      // Every slot loads, in one straight run, so that the loads of a group are
-      // in flight together (a load behind a branch of its own waits for the
-      // ones before it). A slot with no survivor row (erased, or past n - 1)
-      // reads one 16-byte piece of a survivor's window in every lane instead:
-      // one cache line, never an erased cell, and the result is not used.
-#pragma unroll
-      for (int g = kErasedGroup - 1; g >= 0; --g) {
-        const bool take = l0 + g < a.n && !((gone >> g) & 1u);
-        const uint8_t* p = a.rows[take ? l0 + g : spare] + base;
-        const uint32_t lo = take ? lane * 16u : 0u, hi = take ? 1024u : 0u;
-        const u32x4 x = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(p + lo));
-        const u32x4 y = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(p + lo + hi));
-        w[g][0] = x[0]; w[g][1] = x[1]; w[g][2] = x[2]; w[g][3] = x[3];
-        w[g][4] = y[0]; w[g][5] = y[1]; w[g][6] = y[2]; w[g][7] = y[3];
-      }
-#pragma unroll
-      for (int g = kErasedGroup - 1; g >= 0; --g)
-        if (l0 + g < a.n) {
-          const bool live = !((gone >> g) & 1u);
-          if (live) bitslice(w[g]);
-#pragma unroll
-          for (int i = 0; i < P; ++i) {
-#pragma unroll
-            for (int r = 0; r < i; ++r) xtime(acc[i]);
-            if (live) {
-#pragma unroll
-              for (int q = 0; q < 8; ++q) acc[i][q] ^= w[g][q];
-            }
-          }
-        }
-    }
-    // tv = M S: T in rows [0, pp), the erased values in rows [pp, P)
-    uint32_t tv[P][8];
-#pragma unroll
-    for (int i = 0; i < P; ++i)
-#pragma unroll
-      for (int q = 0; q < 8; ++q) tv[i][q] = 0u;
-#pragma unroll
-    for (int i = 0; i < P; ++i) {
-      uint32_t x[8];
-#pragma unroll
-      for (int q = 0; q < 8; ++q) x[q] = acc[i][q];
-      uint32_t cw[2] = {pattern_word(pv, kPatCw + 2 * i), pattern_word(pv, kPatCw + 2 * i + 1)};
-      // bit b of every coefficient: tv[o] ^= alpha^b S_i where it is set. Unrolled
-      // (xtime is then a relabel of the planes) while the body stays small.
-      if constexpr (P <= 4) {
-#pragma unroll
-        for (int b = 0; b < 8; ++b) {
-          if ((cw[0] & (0x01010101u << b)) != 0u) mul_acc_row<P, P>(tv, x, cw, b);
-          if (b < 7) xtime(x);
-        }
-      } else {
-#pragma unroll 1
-        for (int b = 0; b < 8; ++b) {
-          mul_acc_row<P, P>(tv, x, cw, b);
-          xtime(x);
-        }
-      }
-    }
-    uint32_t any = 0u;
-#pragma unroll
-    for (int i = 0; i < P; ++i)
-      if (i < pp) {
-#pragma unroll
-        for (int q = 0; q < 8; ++q) any |= tv[i][q];
-      }
-    const bool dirty = __ballot(any != 0u) != 0ull;  // wave-uniform
-    // the lane's 32 columns are bytes 0..3 of words 0..7 of an un-sliced row;
-    // word x covers window bytes (x >> 2) * 1024 + lane * 16 + (x & 3) * 4
-#pragma unroll
-    for (int i = 0; i < P; ++i)
-      if (dirty || i >= pp) bitslice(tv[i]);
-    if (dirty) {
-#pragma unroll
-      for (int i = 0; i < P; ++i) bitslice(acc[i]);
-      if (any != 0u) {
-#pragma unroll 1
-        for (int x = 0; x < 8; ++x) {
-          uint32_t cur[P], tvx[P];
-#pragma unroll
-          for (int i = 0; i < P; ++i) {
-            uint32_t v = acc[i][0], y = tv[i][0];
-#pragma unroll
-            for (int q = 1; q < 8; ++q) {  // selects, so acc and tv stay in registers
-              v = (x == q) ? acc[i][q] : v;
-              y = (x == q) ? tv[i][q] : y;
-            }
-            cur[i] = v;
-            tvx[i] = y;
-          }
-          uint32_t anyw = 0u;
-#pragma unroll
-          for (int i = 0; i < P; ++i) anyw |= (i < pp) ? tvx[i] : 0u;
-          if (anyw == 0u) continue;
-#pragma unroll 1
-          for (int b = 0; b < 4; ++b) {
-            if (((anyw >> (8 * b)) & 0xFFu) == 0u) continue;
-            uint8_t s[P];
-#pragma unroll
-            for (int i = 0; i < P; ++i) s[i] = static_cast<uint8_t>(cur[i] >> (8 * b));
-            const uint32_t col = static_cast<uint32_t>(off) + (x >> 2) * 1024u + lane * 16u + (x & 3) * 4u + b;
-            uint8_t v[locator::kMaxErased] = {};
-            heal_column<P>(f, a.n, s, ha.pats[ha.pat[stripe]], col, hist, a.rows, stripe * a.stride + col, v);
-            // the column's erased bytes, over the corrected syndromes when it resolved
-#pragma unroll
-            for (int i = 0; i < P; ++i)
-              if (i >= pp) {
-                uint8_t vb = v[0];
-#pragma unroll
-                for (int m = 1; m < P; ++m) vb = (i - pp == m) ? v[m] : vb;
-                tvx[i] = (tvx[i] & ~(0xFFu << (8 * b))) | (static_cast<uint32_t>(vb) << (8 * b));
-              }
-          }
-#pragma unroll
-          for (int i = 0; i < P; ++i)
-#pragma unroll
-            for (int q = 0; q < 8; ++q) tv[i][q] = (x == q) ? tvx[i] : tv[i][q];
-        }
-      }
-    }
-#pragma unroll
-    for (int i = 0; i < P; ++i)
-      if (i >= pp) {
-        const int m = i - pp;
-        const int l = (pattern_word(pv, kPatLoc + (m >> 2)) >> (8 * (m & 3))) & 0xFFu;
-        store_row(const_cast<uint8_t*>(a.rows[l]) + base, lane, tv[i]);
-      }
-    if (!dirty) continue;
-    // flush this window's counts to its stripe (a wave's consecutive windows
-    // can belong to different stripes); the exchange re-arms the histogram
-    __builtin_amdgcn_wave_barrier();
-    uint32_t* rep = a.reports + stripe * a.report_stride;
-    for (int e = lane; e < nwords; e += 64) {
-      const uint32_t v = atomicExch(&hist[e], e == 2 ? kScrubNone : 0u);
-      if (e == 2) {
-        if (v != kScrubNone) atomicMin(&rep[2], v);
-      } else if (v != 0u) {
-        atomicAdd(&rep[e], v);
-      }
-    }
-    __builtin_amdgcn_wave_barrier();
+    heal_window<P>(ha, f, pv, stripe, off, base, lane, hist, nwords, [&] { return ha.pat[stripe]; });
   }
 }
 
-// ------------------------------------------- byte-granular kernel (any alignment)
+// ------------------------------------------- byte-granular kernels (any alignment)
 
 // One column per lane, tables in LDS: rows or strides that are not 16-byte
-// aligned, the row tail (len % 2 KiB) and kernel mode 2. Task idx = stripe *
-// (len - col0) + (column - col0). Counts go straight into the report.
+// aligned, the row tail (len % 2 KiB) and kernel mode 2. Counts go straight
+// into the report. This is the column at rows[l][at] of `stripe`, pattern pt.
+template <int P>
+__device__ __forceinline__ void heal_one_column(const locator::Field& f, const ScrubArgs& a, const ErasePattern& pt,
+                                                uint64_t stripe, uint64_t col, uint64_t at) {
+  uint8_t s[P];
+#pragma unroll
+  for (int i = 0; i < P; ++i) s[i] = 0;
+  for (int l = a.n - 1; l >= 0; --l) {
+    const bool gone = (pt.mask[l >> 5] >> (l & 31)) & 1u;
+    locator::horner_step<P>(f, s, gone ? uint8_t{0} : a.rows[l][at]);
+  }
+  uint8_t v[locator::kMaxErased];
+  heal_column<P>(f, a.n, s, pt, static_cast<uint32_t>(col), a.reports + stripe * a.report_stride, a.rows, at, v);
+  const int e = pt.e;
+  for (int m = 0; m < e; ++m) const_cast<uint8_t*>(a.rows[pt.loc[m]])[at] = v[m];
+}
+
+// Task idx = stripe * (len - col0) + (column - col0).
 template <int P>
 __global__ void __launch_bounds__(kBlockThreads) heal_erased_bytewise_kernel(const HealErasedArgs ha) {
   __shared__ uint8_t s_exp[512];
@@ -302,19 +195,7 @@ __global__ void __launch_bounds__(kBlockThreads) heal_erased_bytewise_kernel(con
        idx += nthreads) {
     const uint64_t stripe = idx / wlen;
     const uint64_t col = a.col0 + (idx - stripe * wlen);
-    const uint64_t at = stripe * a.stride + col;
-    const ErasePattern& pt = ha.pats[ha.pat[stripe]];
-    uint8_t s[P];
-#pragma unroll
-    for (int i = 0; i < P; ++i) s[i] = 0;
-    for (int l = a.n - 1; l >= 0; --l) {
-      const bool gone = (pt.mask[l >> 5] >> (l & 31)) & 1u;
-      locator::horner_step<P>(f, s, gone ? uint8_t{0} : a.rows[l][at]);
-    }
-    uint8_t v[locator::kMaxErased];
-    heal_column<P>(f, a.n, s, pt, static_cast<uint32_t>(col), a.reports + stripe * a.report_stride, a.rows, at, v);
-    const int e = pt.e;
-    for (int m = 0; m < e; ++m) const_cast<uint8_t*>(a.rows[pt.loc[m]])[at] = v[m];
+    heal_one_column<P>(f, a, ha.pats[ha.pat[stripe]], stripe, col, stripe * a.stride + col);
   }
 }
 
@@ -339,22 +220,17 @@ hipError_t launch_columns(const HealErasedArgs& a, hipStream_t s) {
 
 // ------------------------------------------------------ the listed form
 //
-// Checked repair (hrs_repair_checked_dev) runs the two kernels above over the
-// stripes a device list names (HealListedArgs, hrs_heal_erased.hpp). They are
-// copies of the walks, not a template flag on them: with the flag the compiler
-// allocated the existing kernels' registers differently (111 -> 96 VGPRs at
-// P = 1, another occupancy at P = 1 and 3), and the batch calls keep the code
-// they were measured with. What differs: the task range is count * nwin, the
-// count read from device memory at kernel entry and clamped to nstripes; a
-// task's stripe is the list's entry, which is also its pattern's index; an
-// entry that is no stripe of the batch is skipped and never indexed with; a
-// block with no task leaves before it loads anything.
-
-// How many stripes the list names, never more than the batch has.
-__device__ __forceinline__ uint64_t listed_count(const HealListedArgs& a) {
-  const uint32_t count = a.list[0];
-  return count < a.nstripes ? count : a.nstripes;
-}
+// Checked repair (hrs_repair_checked_dev) runs the two walks above over the
+// stripes a device list names (HealListedArgs, hrs_heal_erased.hpp). The
+// kernels are instantiations of their own, not a template flag on the two
+// above: with the flag the compiler allocated the existing kernels' registers
+// differently (111 -> 96 VGPRs at P = 1, another occupancy at P = 1 and 3),
+// and the batch calls keep the code they were measured with. What differs is
+// the prologue: the task range is count * nwin, the count read from device
+// memory at kernel entry and clamped to nstripes; a task's stripe is the
+// list's entry, which is also its pattern's index; an entry that is no stripe
+// of the batch is skipped and never indexed with; a block with no task leaves
+// before it loads anything.
 
 // The stripe at a place of the list; the caller tests it against nstripes
 // before it indexes anything with it.
@@ -370,39 +246,34 @@ template <int P>
 __global__ void __launch_bounds__(kBlockThreads) heal_listed_kernel(const HealListedArgs la) {
   __shared__ uint8_t s_exp[512];
   __shared__ uint8_t s_log[256];
-  __shared__ uint32_t s_hist[kWavesPerBlock][kScrubHead + kScrubMaxRows];
+  __shared__ uint32_t s_hist[kWavesPerBlock][kHistWords];
   const HealErasedArgs& ha = la.h;
   const ScrubArgs& a = ha.s;
   // the task range comes from device memory (a.ntasks is only the bound the
   // grid was sized for); a block whose first wave has no window leaves before
   // it loads anything (block-uniform)
-  const uint64_t ntasks = listed_count(la) * a.nwin;
+  const uint64_t ntasks = static_cast<uint64_t>(listed_count(la.list, la.nstripes)) * a.nwin;
   {
     const WaveTasks w0 = wave_tasks(ntasks, a.order);
     if (w0.t0 - (threadIdx.x >> 6) >= w0.end) return;
   }
   load_tables(s_exp, s_log);
-  const int nwords = kScrubHead + a.n;
-  for (int i = threadIdx.x; i < kWavesPerBlock * (kScrubHead + kScrubMaxRows); i += blockDim.x) {
-    const int e = i % (kScrubHead + kScrubMaxRows);
-    s_hist[i / (kScrubHead + kScrubMaxRows)][e] = e == 2 ? kScrubNone : 0u;
-  }
+  init_hist(s_hist);
   __syncthreads();
   const locator::Field f{s_exp, s_log};
   const int lane = threadIdx.x & 63;
   uint32_t* hist = s_hist[threadIdx.x >> 6];
+  const int nwords = kScrubHead + a.n;
   const WaveTasks wt = wave_tasks(ntasks, a.order);
-  // Two loads lead to a window's pattern (its stripe's index, then the table
-  // entry); both run ahead of the windows so that neither is waited for: while
-  // window j runs, the entry of window j + 1 and the index of window j + 2
-  // are in flight; here the first load is the list's entry, which is the index.
+  // The pattern's prefetch chain of heal_erased_kernel; here the first load is
+  // the list's entry, which is the index.
   uint64_t pos_cur = 0, pos_next = 0, stripe_cur = 0, stripe_next = 0;
   uint32_t pv_next = 0u;
   int32_t pi_next = 0;
   if (wt.at(0) < wt.end) {
     pos_cur = wt.at(0) / a.nwin;
     stripe_cur = listed_stripe(la, pos_cur);
-    pv_next = load_pattern(ha, listed_pattern(la, stripe_cur), lane);
+    pv_next = load_pattern(ha.pats, listed_pattern(la, stripe_cur), lane);
   }
   if (wt.at(1) < wt.end) {
     pos_next = wt.at(1) / a.nwin;
@@ -418,165 +289,14 @@ __global__ void __launch_bounds__(kBlockThreads) heal_listed_kernel(const HealLi
     const uint32_t pv = pv_next;
     pos_cur = pos_next;
     stripe_cur = stripe_next;
-    if (wt.at(j + 1) < wt.end) pv_next = load_pattern(ha, pi_next, lane);
+    if (wt.at(j + 1) < wt.end) pv_next = load_pattern(ha.pats, pi_next, lane);
     if (wt.at(j + 2) < wt.end) {
       pos_next = wt.at(j + 2) / a.nwin;
       stripe_next = listed_stripe(la, pos_next);
       pi_next = listed_pattern(la, stripe_next);
     }
     if (stripe >= la.nstripes) continue;  // no stripe of this batch: nothing is indexed with it
-    const int pp = P - static_cast<int>(pattern_word(pv, kPatE));  // wave-uniform, like every field
-    const int spare = static_cast<int>(pattern_word(pv, kPatSpare));
-    uint32_t acc[P][8];
-#pragma unroll
-    for (int i = 0; i < P; ++i)
-#pragma unroll
-      for (int q = 0; q < 8; ++q) acc[i][q] = 0u;
-    for (int l0 = (a.n - 1) & ~(kErasedGroup - 1); l0 >= 0; l0 -= kErasedGroup) {
-      // locations l0 + 7 .. l0; bit g of `gone`: l0 + g is erased
-      const uint32_t gone = (pattern_word(pv, kPatMask + (l0 >> 5)) >> (l0 & 31)) & ((1u << kErasedGroup) - 1u);
-      uint32_t w[kErasedGroup][8];
-      // Every slot loads, in one straight run, so that the loads of a group are
-      // in flight together (a load behind a branch of its own waits for the
-      // ones before it). A slot with no survivor row (erased, or past n - 1)
-      // reads one 16-byte piece of a survivor's window in every lane instead:
-      // one cache line, never an erased cell, and the result is not used.
-#pragma unroll
-      for (int g = kErasedGroup - 1; g >= 0; --g) {
-        const bool take = l0 + g < a.n && !((gone >> g) & 1u);
-        const uint8_t* p = a.rows[take ? l0 + g : spare] + base;
-        const uint32_t lo = take ? lane * 16u : 0u, hi = take ? 1024u : 0u;
-        const u32x4 x = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(p + lo));
-        const u32x4 y = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(p + lo + hi));
-        w[g][0] = x[0]; w[g][1] = x[1]; w[g][2] = x[2]; w[g][3] = x[3];
-        w[g][4] = y[0]; w[g][5] = y[1]; w[g][6] = y[2]; w[g][7] = y[3];
-      }
-#pragma unroll
-      for (int g = kErasedGroup - 1; g >= 0; --g)
-        if (l0 + g < a.n) {
-          const bool live = !((gone >> g) & 1u);
-          if (live) bitslice(w[g]);
-#pragma unroll
-          for (int i = 0; i < P; ++i) {
-#pragma unroll
-            for (int r = 0; r < i; ++r) xtime(acc[i]);
-            if (live) {
-#pragma unroll
-              for (int q = 0; q < 8; ++q) acc[i][q] ^= w[g][q];
-            }
-          }
-        }
-    }
-    // tv = M S: T in rows [0, pp), the erased values in rows [pp, P)
-    uint32_t tv[P][8];
-#pragma unroll
-    for (int i = 0; i < P; ++i)
-#pragma unroll
-      for (int q = 0; q < 8; ++q) tv[i][q] = 0u;
-#pragma unroll
-    for (int i = 0; i < P; ++i) {
-      uint32_t x[8];
-#pragma unroll
-      for (int q = 0; q < 8; ++q) x[q] = acc[i][q];
-      uint32_t cw[2] = {pattern_word(pv, kPatCw + 2 * i), pattern_word(pv, kPatCw + 2 * i + 1)};
-      // bit b of every coefficient: tv[o] ^= alpha^b S_i where it is set. Unrolled
-      // (xtime is then a relabel of the planes) while the body stays small.
-      if constexpr (P <= 4) {
-#pragma unroll
-        for (int b = 0; b < 8; ++b) {
-          if ((cw[0] & (0x01010101u << b)) != 0u) mul_acc_row<P, P>(tv, x, cw, b);
-          if (b < 7) xtime(x);
-        }
-      } else {
-#pragma unroll 1
-        for (int b = 0; b < 8; ++b) {
-          mul_acc_row<P, P>(tv, x, cw, b);
-          xtime(x);
-        }
-      }
-    }
-    uint32_t any = 0u;
-#pragma unroll
-    for (int i = 0; i < P; ++i)
-      if (i < pp) {
-#pragma unroll
-        for (int q = 0; q < 8; ++q) any |= tv[i][q];
-      }
-    const bool dirty = __ballot(any != 0u) != 0ull;  // wave-uniform
-    // the lane's 32 columns are bytes 0..3 of words 0..7 of an un-sliced row;
-    // word x covers window bytes (x >> 2) * 1024 + lane * 16 + (x & 3) * 4
-#pragma unroll
-    for (int i = 0; i < P; ++i)
-      if (dirty || i >= pp) bitslice(tv[i]);
-    if (dirty) {
-#pragma unroll
-      for (int i = 0; i < P; ++i) bitslice(acc[i]);
-      if (any != 0u) {
-#pragma unroll 1
-        for (int x = 0; x < 8; ++x) {
-          uint32_t cur[P], tvx[P];
-#pragma unroll
-          for (int i = 0; i < P; ++i) {
-            uint32_t v = acc[i][0], y = tv[i][0];
-#pragma unroll
-            for (int q = 1; q < 8; ++q) {  // selects, so acc and tv stay in registers
-              v = (x == q) ? acc[i][q] : v;
-              y = (x == q) ? tv[i][q] : y;
-            }
-            cur[i] = v;
-            tvx[i] = y;
-          }
-          uint32_t anyw = 0u;
-#pragma unroll
-          for (int i = 0; i < P; ++i) anyw |= (i < pp) ? tvx[i] : 0u;
-          if (anyw == 0u) continue;
-#pragma unroll 1
-          for (int b = 0; b < 4; ++b) {
-            if (((anyw >> (8 * b)) & 0xFFu) == 0u) continue;
-            uint8_t s[P];
-#pragma unroll
-            for (int i = 0; i < P; ++i) s[i] = static_cast<uint8_t>(cur[i] >> (8 * b));
-            const uint32_t col = static_cast<uint32_t>(off) + (x >> 2) * 1024u + lane * 16u + (x & 3) * 4u + b;
-            uint8_t v[locator::kMaxErased] = {};
-            heal_column<P>(f, a.n, s, ha.pats[listed_pattern(la, stripe)], col, hist, a.rows, stripe * a.stride + col, v);
-            // the column's erased bytes, over the corrected syndromes when it resolved
-#pragma unroll
-            for (int i = 0; i < P; ++i)
-              if (i >= pp) {
-                uint8_t vb = v[0];
-#pragma unroll
-                for (int m = 1; m < P; ++m) vb = (i - pp == m) ? v[m] : vb;
-                tvx[i] = (tvx[i] & ~(0xFFu << (8 * b))) | (static_cast<uint32_t>(vb) << (8 * b));
-              }
-          }
-#pragma unroll
-          for (int i = 0; i < P; ++i)
-#pragma unroll
-            for (int q = 0; q < 8; ++q) tv[i][q] = (x == q) ? tvx[i] : tv[i][q];
-        }
-      }
-    }
-#pragma unroll
-    for (int i = 0; i < P; ++i)
-      if (i >= pp) {
-        const int m = i - pp;
-        const int l = (pattern_word(pv, kPatLoc + (m >> 2)) >> (8 * (m & 3))) & 0xFFu;
-        store_row(const_cast<uint8_t*>(a.rows[l]) + base, lane, tv[i]);
-      }
-    if (!dirty) continue;
-    // flush this window's counts to its stripe (a wave's consecutive windows
-    // can belong to different stripes); the exchange re-arms the histogram
-    __builtin_amdgcn_wave_barrier();
-    uint32_t* rep = a.reports + stripe * a.report_stride;
-    for (int e = lane; e < nwords; e += 64) {
-      const uint32_t v = atomicExch(&hist[e], e == 2 ? kScrubNone : 0u);
-      if (e == 2) {
-        if (v != kScrubNone) atomicMin(&rep[2], v);
-      } else if (v != 0u) {
-        atomicAdd(&rep[e], v);
-      }
-    }
-    __builtin_amdgcn_wave_barrier();
+    heal_window<P>(ha, f, pv, stripe, off, base, lane, hist, nwords, [&] { return listed_pattern(la, stripe); });
   }
 }
 
@@ -587,7 +307,7 @@ __global__ void __launch_bounds__(kBlockThreads) heal_listed_bytewise_kernel(con
   const HealErasedArgs& ha = la.h;
   const ScrubArgs& a = ha.s;
   const uint64_t wlen = a.len - a.col0;
-  const uint64_t ntasks = listed_count(la) * wlen;
+  const uint64_t ntasks = static_cast<uint64_t>(listed_count(la.list, la.nstripes)) * wlen;
   if (static_cast<uint64_t>(blockIdx.x) * blockDim.x >= ntasks) return;  // block-uniform, before any load
   load_tables(s_exp, s_log);
   __syncthreads();
@@ -598,19 +318,7 @@ __global__ void __launch_bounds__(kBlockThreads) heal_listed_bytewise_kernel(con
     const uint64_t stripe = listed_stripe(la, pos);
     if (stripe >= la.nstripes) continue;  // no stripe of this batch: nothing is indexed with it
     const uint64_t col = a.col0 + (idx - pos * wlen);
-    const uint64_t at = stripe * a.stride + col;
-    const ErasePattern& pt = ha.pats[listed_pattern(la, stripe)];
-    uint8_t s[P];
-#pragma unroll
-    for (int i = 0; i < P; ++i) s[i] = 0;
-    for (int l = a.n - 1; l >= 0; --l) {
-      const bool gone = (pt.mask[l >> 5] >> (l & 31)) & 1u;
-      locator::horner_step<P>(f, s, gone ? uint8_t{0} : a.rows[l][at]);
-    }
-    uint8_t v[locator::kMaxErased];
-    heal_column<P>(f, a.n, s, pt, static_cast<uint32_t>(col), a.reports + stripe * a.report_stride, a.rows, at, v);
-    const int e = pt.e;
-    for (int m = 0; m < e; ++m) const_cast<uint8_t*>(a.rows[pt.loc[m]])[at] = v[m];
+    heal_one_column<P>(f, a, ha.pats[listed_pattern(la, stripe)], stripe, col, stripe * a.stride + col);
   }
 }
 
@@ -636,42 +344,20 @@ hipError_t launch_listed_columns(const HealListedArgs& a, hipStream_t s) {
 
 }  // namespace
 
-#define HRS_HEAL_ERASED_DISPATCH(fn)   \
-  switch (a.s.p) {                     \
-    case 1: return fn<1>(a, s);        \
-    case 2: return fn<2>(a, s);        \
-    case 3: return fn<3>(a, s);        \
-    case 4: return fn<4>(a, s);        \
-    case 5: return fn<5>(a, s);        \
-    case 6: return fn<6>(a, s);        \
-    case 7: return fn<7>(a, s);        \
-    case 8: return fn<8>(a, s);        \
-    default: return hipErrorInvalidValue; \
-  }
+hipError_t launch_heal_erased(const HealErasedArgs& a, hipStream_t s) {
+  return dispatch_p<1, 8>(a.s.p, [&](auto P) { return launch_windows<P>(a, s); });
+}
 
-hipError_t launch_heal_erased(const HealErasedArgs& a, hipStream_t s) { HRS_HEAL_ERASED_DISPATCH(launch_windows) }
+hipError_t launch_heal_erased_bytewise(const HealErasedArgs& a, hipStream_t s) {
+  return dispatch_p<1, 8>(a.s.p, [&](auto P) { return launch_columns<P>(a, s); });
+}
 
-hipError_t launch_heal_erased_bytewise(const HealErasedArgs& a, hipStream_t s) { HRS_HEAL_ERASED_DISPATCH(launch_columns) }
+hipError_t launch_heal_listed(const HealListedArgs& a, hipStream_t s) {
+  return dispatch_p<1, 8>(a.h.s.p, [&](auto P) { return launch_listed_windows<P>(a, s); });
+}
 
-#undef HRS_HEAL_ERASED_DISPATCH
-
-#define HRS_HEAL_LISTED_DISPATCH(fn)   \
-  switch (a.h.s.p) {                   \
-    case 1: return fn<1>(a, s);        \
-    case 2: return fn<2>(a, s);        \
-    case 3: return fn<3>(a, s);        \
-    case 4: return fn<4>(a, s);        \
-    case 5: return fn<5>(a, s);        \
-    case 6: return fn<6>(a, s);        \
-    case 7: return fn<7>(a, s);        \
-    case 8: return fn<8>(a, s);        \
-    default: return hipErrorInvalidValue; \
-  }
-
-hipError_t launch_heal_listed(const HealListedArgs& a, hipStream_t s) { HRS_HEAL_LISTED_DISPATCH(launch_listed_windows) }
-
-hipError_t launch_heal_listed_bytewise(const HealListedArgs& a, hipStream_t s) { HRS_HEAL_LISTED_DISPATCH(launch_listed_columns) }
-
-#undef HRS_HEAL_LISTED_DISPATCH
+hipError_t launch_heal_listed_bytewise(const HealListedArgs& a, hipStream_t s) {
+  return dispatch_p<1, 8>(a.h.s.p, [&](auto P) { return launch_listed_columns<P>(a, s); });
+}
 
 }  // namespace hrs

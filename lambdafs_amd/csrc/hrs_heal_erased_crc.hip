@@ -8,7 +8,9 @@
 // The walk is heal_erased_kernel's (hrs_heal_erased.hip): one wave per 2 KiB
 // window, the stripe's pattern in the lanes (fields by v_readlane), Horner
 // over the rows from location n - 1 down in the bit-sliced domain, an erased
-// row not loaded and taking the xtime-only step, tv = M S. The CRC side is
+// row not loaded and taking the xtime-only step, then the tail both kernels
+// run (heal_tail, hrs_heal_erased_device.hpp): tv = M S, the ballot, the bad
+// columns. The CRC side is
 // scrub_crc_kernel's (hrs_scrub_crc.hip): before a survivor row is sliced its
 // eight words feed the lane's two piece chains, the Z_1024 join and the lane
 // tree, the chains of a group in lockstep; lane 0 writes the raw window CRC to
@@ -36,6 +38,7 @@
 #include "hrs_crc.hpp"
 #include "hrs_device.hpp"
 #include "hrs_heal_erased.hpp"
+#include "hrs_heal_erased_device.hpp"
 #include "hrs_launch.hpp"
 #include "hrs_locator.hpp"
 #include "hrs_scrub_device.hpp"
@@ -50,49 +53,6 @@ constexpr size_t heal_erased_crc_lds_bytes(int threads) {
   return (static_cast<size_t>(kCrcLdsWordsA) + kFieldWords + static_cast<size_t>(threads / 64) * kHistWords) * 4;
 }
 static_assert(heal_erased_crc_lds_bytes(1024) <= 163840, "the CRC image, the field tables and 16 histograms fit one CU's LDS");
-
-// heal_column of hrs_heal_erased.hip (that unit keeps its text):
-// the locator on one bad column, the survivors patched, the counters at h.
-template <int P>
-__device__ __forceinline__ void heal_column(const locator::Field& f, int n, const uint8_t (&s)[P],
-                                            const ErasePattern& pt, uint32_t col, uint32_t* h,
-                                            const uint8_t* const* rows, uint64_t at,
-                                            uint8_t (&v)[locator::kMaxErased]) {
-  int nloc = 0;
-  uint8_t loc[locator::kMaxErrors], u[locator::kMaxErrors];
-  const int state = locator::locate_errata<P>(f, n, s, pt.e, pt.loc, pt.gamma, &nloc, loc, u, v);
-  if (state == locator::kConsistent) return;
-  atomicAdd(&h[0], 1u);
-  atomicMin(&h[2], col);
-  if (state == locator::kUnresolved) {
-    atomicAdd(&h[1], 1u);
-    return;
-  }
-  uint32_t patched = 0u;
-  for (int j = 0; j < nloc; ++j) {
-    atomicAdd(&h[kScrubHead + loc[j]], 1u);
-    if (u[j] != 0) {
-      uint8_t* q = const_cast<uint8_t*>(rows[loc[j]]) + at;
-      *q = static_cast<uint8_t>(*q ^ u[j]);
-      ++patched;
-    }
-  }
-  if (patched != 0u) atomicAdd(&h[kScrubPatched], patched);
-}
-
-// The calling wave's copy of its stripe's pattern, as in heal_erased_kernel:
-// lane j % 32 holds dword j of the 128-byte table entry.
-constexpr int kPatE = offsetof(ErasePattern, e) / 4, kPatMask = offsetof(ErasePattern, mask) / 4,
-              kPatCw = offsetof(ErasePattern, cw) / 4, kPatLoc = offsetof(ErasePattern, loc) / 4, kPatSpare = offsetof(ErasePattern, spare) / 4;
-static_assert(sizeof(ErasePattern) == 128 && offsetof(ErasePattern, cw) % 8 == 0, "one dword per lane of a half wave");
-
-__device__ __forceinline__ uint32_t load_pattern(const HealErasedCrcArgs& ha, int32_t index, int lane) {
-  return reinterpret_cast<const uint32_t*>(ha.pats + index)[lane & 31];
-}
-
-__device__ __forceinline__ uint32_t pattern_word(uint32_t pv, int word) {
-  return static_cast<uint32_t>(__builtin_amdgcn_readlane(static_cast<int>(pv), word));
-}
 
 // The raw CRC of the window whose un-sliced words the lane holds in w.
 __device__ __forceinline__ uint32_t window_crc(const SliceTab& slices, const uint32_t* zchunk, const uint32_t* tree,
@@ -212,7 +172,7 @@ __global__ void __launch_bounds__(THREADS) heal_erased_crc_kernel(const HealEras
   int32_t pi_next = 0;
   if (wt.at(0) < wt.end) {
     stripe_cur = wt.at(0) / a.nwin;
-    pv_next = load_pattern(ha, ha.pat[stripe_cur], lane);
+    pv_next = load_pattern(ha.pats, ha.pat[stripe_cur], lane);
   }
   if (wt.at(1) < wt.end) {
     stripe_next = wt.at(1) / a.nwin;
@@ -228,12 +188,11 @@ __global__ void __launch_bounds__(THREADS) heal_erased_crc_kernel(const HealEras
     const uint64_t raw_at = stripe * a.n * a.nwin + win;  // + l * nwin: raw[(stripe * n + l) * nwin + win]
     const uint32_t pv = pv_next;
     stripe_cur = stripe_next;
-    if (wt.at(j + 1) < wt.end) pv_next = load_pattern(ha, pi_next, lane);
+    if (wt.at(j + 1) < wt.end) pv_next = load_pattern(ha.pats, pi_next, lane);
     if (wt.at(j + 2) < wt.end) {
       stripe_next = wt.at(j + 2) / a.nwin;
       pi_next = ha.pat[stripe_next];
     }
-    const int pp = P - static_cast<int>(pattern_word(pv, kPatE));  // wave-uniform, like every field
     const int spare = static_cast<int>(pattern_word(pv, kPatSpare));
     const uint32_t mask0 = pattern_word(pv, kPatMask);
     uint32_t acc[P][8];
@@ -257,94 +216,18 @@ __global__ void __launch_bounds__(THREADS) heal_erased_crc_kernel(const HealEras
       }
     if constexpr (G > 1)
       if (top & 1) rows_group<P, 1>(a, top, gone_bits(mask0, top, 1), spare, base, raw_at, lane, slices, zchunk, tree, acc);
-    // tv = M S: T in rows [0, pp), the erased values in rows [pp, P)
-    uint32_t tv[P][8];
-#pragma unroll
-    for (int i = 0; i < P; ++i)
-#pragma unroll
-      for (int q = 0; q < 8; ++q) tv[i][q] = 0u;
-#pragma unroll
-    for (int i = 0; i < P; ++i) {
-      uint32_t x[8];
-#pragma unroll
-      for (int q = 0; q < 8; ++q) x[q] = acc[i][q];
-      uint32_t cw[2] = {pattern_word(pv, kPatCw + 2 * i), pattern_word(pv, kPatCw + 2 * i + 1)};
-#pragma unroll
-      for (int b = 0; b < 8; ++b) {
-        if ((cw[0] & (0x01010101u << b)) != 0u) mul_acc_row<P, P>(tv, x, cw, b);
-        if (b < 7) xtime(x);
-      }
-    }
-    uint32_t any = 0u;
-#pragma unroll
-    for (int i = 0; i < P; ++i)
-      if (i < pp) {
-#pragma unroll
-        for (int q = 0; q < 8; ++q) any |= tv[i][q];
-      }
-    const bool dirty = __ballot(any != 0u) != 0ull;  // wave-uniform
-#pragma unroll
-    for (int i = 0; i < P; ++i)
-      if (dirty || i >= pp) bitslice(tv[i]);
-    if (dirty) {
-#pragma unroll
-      for (int i = 0; i < P; ++i) bitslice(acc[i]);
-      if (any != 0u) {
-#pragma unroll 1
-        for (int x = 0; x < 8; ++x) {
-          uint32_t cur[P], tvx[P];
-#pragma unroll
-          for (int i = 0; i < P; ++i) {
-            uint32_t v = acc[i][0], y = tv[i][0];
-#pragma unroll
-            for (int q = 1; q < 8; ++q) {  // selects, so acc and tv stay in registers
-              v = (x == q) ? acc[i][q] : v;
-              y = (x == q) ? tv[i][q] : y;
-            }
-            cur[i] = v;
-            tvx[i] = y;
+    // a clean window's erased rows give their raw words before they are
+    // stored; a dirty window's words come from the redo kernel
+    const bool dirty = heal_tail<P>(
+        f, a.n, a.rows, ha.pats, pv, stripe * a.stride, static_cast<uint32_t>(off), lane, hist, acc,
+        [&] { return ha.pat[stripe]; },
+        [&](int l, const uint32_t(&row)[8], bool dirty_window) {
+          if (!dirty_window) {
+            const uint32_t c = window_crc(slices, zchunk, tree, row);
+            if (lane == 0) a.raw[raw_at + static_cast<uint64_t>(l) * a.nwin] = c;
           }
-          uint32_t anyw = 0u;
-#pragma unroll
-          for (int i = 0; i < P; ++i) anyw |= (i < pp) ? tvx[i] : 0u;
-          if (anyw == 0u) continue;
-#pragma unroll 1
-          for (int b = 0; b < 4; ++b) {
-            if (((anyw >> (8 * b)) & 0xFFu) == 0u) continue;
-            uint8_t s[P];
-#pragma unroll
-            for (int i = 0; i < P; ++i) s[i] = static_cast<uint8_t>(cur[i] >> (8 * b));
-            const uint32_t col = static_cast<uint32_t>(off) + (x >> 2) * 1024u + lane * 16u + (x & 3) * 4u + b;
-            uint8_t v[locator::kMaxErased] = {};
-            heal_column<P>(f, a.n, s, ha.pats[ha.pat[stripe]], col, hist, a.rows, stripe * a.stride + col, v);
-            // the column's erased bytes, over the corrected syndromes when it resolved
-#pragma unroll
-            for (int i = 0; i < P; ++i)
-              if (i >= pp) {
-                uint8_t vb = v[0];
-#pragma unroll
-                for (int m = 1; m < P; ++m) vb = (i - pp == m) ? v[m] : vb;
-                tvx[i] = (tvx[i] & ~(0xFFu << (8 * b))) | (static_cast<uint32_t>(vb) << (8 * b));
-              }
-          }
-#pragma unroll
-          for (int i = 0; i < P; ++i)
-#pragma unroll
-            for (int q = 0; q < 8; ++q) tv[i][q] = (x == q) ? tvx[i] : tv[i][q];
-        }
-      }
-    }
-#pragma unroll
-    for (int i = 0; i < P; ++i)
-      if (i >= pp) {
-        const int m = i - pp;
-        const int l = (pattern_word(pv, kPatLoc + (m >> 2)) >> (8 * (m & 3))) & 0xFFu;
-        if (!dirty) {  // a dirty window's words come from the redo kernel
-          const uint32_t c = window_crc(slices, zchunk, tree, tv[i]);
-          if (lane == 0) a.raw[raw_at + static_cast<uint64_t>(l) * a.nwin] = c;
-        }
-        store_row(const_cast<uint8_t*>(a.rows[l]) + base, lane, tv[i]);
-      }
+          store_row(const_cast<uint8_t*>(a.rows[l]) + base, lane, row);
+        });
     if (!dirty) continue;
     __builtin_amdgcn_wave_barrier();
     if (lane == 0) {

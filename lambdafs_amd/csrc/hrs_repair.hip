@@ -10,8 +10,9 @@
 //    fill_pattern, its working room in LDS), empties its report for pass 2 and
 //    appends it to the list: one atomic per wave (ballot, the leader adds the
 //    count, every listed lane takes its rank).
-//  - repair_crc_window_kernel: crc_window_kernel's walk (hrs_crc.hip) over the
-//    cells of the listed stripes, as pass 2 left them.
+//  - repair_crc_window_kernel: the 32 KiB window walk of crc_window_kernel
+//    (crc_window_raw, hrs_device.hpp) over the cells of the listed stripes, as
+//    pass 2 left them.
 //  - repair_fold_verdict_kernel: one wave per listed stripe folds its cells'
 //    window CRCs, overwrites the stripe's crc_out words and applies step 6.
 //
@@ -23,6 +24,7 @@
 #include <hip/hip_runtime.h>
 
 #include "hrs_device.hpp"
+#include "hrs_heal_erased_device.hpp"
 #include "hrs_launch.hpp"
 #include "hrs_repair.hpp"
 #include "hrs_repair_rule.hpp"
@@ -32,11 +34,6 @@ namespace hrs {
 namespace {
 
 constexpr int kPlanThreads = 64;  // one wave: PatternWork per thread in LDS (12 KiB)
-
-__device__ __forceinline__ uint32_t listed_count(const uint32_t* list, uint32_t nstripes) {
-  const uint32_t count = list[0];
-  return count < nstripes ? count : nstripes;
-}
 
 __global__ void __launch_bounds__(kPlanThreads) repair_plan_kernel(const RepairPlanArgs a) {
   __shared__ uint8_t s_exp[512];
@@ -96,7 +93,7 @@ __global__ void __launch_bounds__(kPlanThreads) repair_plan_kernel(const RepairP
 
 // ---- CRCs of the listed stripes
 
-// crc_window_kernel (hrs_crc.hip) with the stripe taken from the list: task
+// crc_window_kernel's tasks (hrs_crc.hip) with the stripe taken from the list: task
 // t = ((i * n + l) * wpr + w) for window w of cell l of the i-th listed stripe.
 template <bool ALIGNED>
 __global__ void __launch_bounds__(kCrcBlockThreads) repair_crc_window_kernel(const RepairCrcArgs a) {
@@ -123,54 +120,14 @@ __global__ void __launch_bounds__(kCrcBlockThreads) repair_crc_window_kernel(con
     const uint64_t stripe = a.list[1 + place];
     if (stripe >= a.nstripes) continue;  // no stripe of this batch: nothing is indexed with it
     const uint8_t* base = a.rows[row] + stripe * a.stride;
-    // the window covers [end - kCrcWindow, end); bytes below lo read as zero
-    const bool full = w < nwin;
-    const int64_t end = full ? static_cast<int64_t>((w + 1) * kCrcWindow) : static_cast<int64_t>(a.len);
-    const int64_t lo = full ? static_cast<int64_t>(w * kCrcWindow) : static_cast<int64_t>(nwin * kCrcWindow);
-    const int64_t start = end - kCrcWindow + lane * crc::kPieceBytes;
-    uint32_t c = 0;
-#pragma unroll 1
-    for (int g = 0; g < crc::kPieces; g += kCrcGroup) {
-      uint32_t words[kCrcGroup][4];
-#pragma unroll
-      for (int q = 0; q < kCrcGroup; ++q) {
-        const int64_t pos0 = start + static_cast<int64_t>(g + q) * crc::kChunkBytes;
-        if (ALIGNED && full) {
-          const u32x4 v = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(base + pos0));
-          words[q][0] = v[0];
-          words[q][1] = v[1];
-          words[q][2] = v[2];
-          words[q][3] = v[3];
-        } else {
-#pragma unroll
-          for (int k = 0; k < 4; ++k) {
-            uint32_t x = 0;
-#pragma unroll
-            for (int b = 0; b < 4; ++b) {
-              const int64_t pos = pos0 + 4 * k + b;
-              if (pos >= lo) x |= static_cast<uint32_t>(base[pos]) << (8 * b);
-            }
-            words[q][k] = x;
-          }
-        }
-      }
-      uint32_t ch[kCrcGroup];
-#pragma unroll
-      for (int q = 0; q < kCrcGroup; ++q) ch[q] = 0u;
-#pragma unroll
-      for (int st = 0; st < 4; ++st)
-#pragma unroll
-        for (int q = 0; q < kCrcGroup; ++q) ch[q] = slice4(slices, ch[q] ^ words[q][st]);
-#pragma unroll
-      for (int q = 0; q < kCrcGroup; ++q) c = (g + q == 0) ? ch[q] : (zmul(zchunk, c) ^ ch[q]);
-    }
-    c = lane_tree(tree, c);
+    const uint32_t c = crc_window_raw<ALIGNED>(base, w, nwin, a.len, lane, slices, zchunk, tree);
     if (lane == 0) a.raw[sr * wpr + w] = c;
   }
 }
 
-// crc_fold_kernel's fold (hrs_crc.hip), one wave per listed stripe over its n
-// cells in turn; lane 0 then knows F and F ∩ D of the whole stripe.
+// The fold of crc_fold_kernel (fold_row, hrs_device.hpp), one wave per listed
+// stripe over its n cells in turn; lane 0 then knows F and F ∩ D of the whole
+// stripe.
 __global__ void __launch_bounds__(256) repair_fold_verdict_kernel(const RepairFoldArgs a) {
   extern __shared__ __attribute__((aligned(16))) uint32_t lds[];
   const uint32_t count = listed_count(a.list, a.nstripes);
@@ -191,14 +148,8 @@ __global__ void __launch_bounds__(256) repair_fold_verdict_kernel(const RepairFo
     bool any_f = false, any_fd = false;
     for (int l = 0; l < a.n; ++l) {
       const uint32_t* raw = a.raw + (static_cast<uint64_t>(place) * a.n + l) * wpr;
-      uint32_t c = 0;
-      for (int g = 0; g < a.G; ++g) {
-        const int64_t w = static_cast<int64_t>(lane) * a.G + g - static_cast<int64_t>(pad);
-        if (w >= 0) c = zmul(zw, c) ^ raw[w];
-      }
-      c = lane_tree(ztree, c);
+      const uint32_t c = fold_row(raw, a.nwin, a.G, pad, a.tail, zw, ztree, ztail, lane);
       if (lane == 0) {
-        if (a.tail) c = zmul(ztail, c) ^ raw[a.nwin];
         const uint32_t now = zmul(zlen, 0xFFFFFFFFu) ^ c ^ 0xFFFFFFFFu;
         const uint64_t at = stripe * a.n + l;
         const uint32_t stored = a.stored[at];
