@@ -112,7 +112,8 @@ void run_shape(int k, int p, int ncols, int per, unsigned seed) {
 
 int main() {
   const int shapes[][4] = {{10, 4, 600, 60}, {12, 4, 600, 60}, {6, 3, 600, 60}, {3, 2, 600, 60},
-                           {4, 1, 600, 60},  {20, 8, 600, 60}, {247, 8, 60, 10}};
+                           {4, 1, 600, 60},  {20, 8, 600, 60}, {247, 8, 60, 10}, {6, 5, 600, 60},
+                           {7, 6, 600, 60},  {10, 7, 600, 60}};
   unsigned seed = 211;
   for (const auto& s : shapes) run_shape(s[0], s[1], s[2], s[3], seed++);
   // argument errors on a host-only handle

@@ -20,7 +20,7 @@ from lambdafs_amd import device
 
 CLEAN, REPAIRED, RESTAMP, FAILED, TOOMANY, AMBIGUOUS = range(6)
 NONE = 0xFFFFFFFF
-CODES = [(3, 2), (6, 3), (10, 4), (4, 1), (12, 8)]
+CODES = [(3, 2), (6, 3), (10, 4), (4, 1), (12, 8), (6, 5), (7, 6), (10, 7)]
 
 
 def crc(row):

@@ -3,8 +3,9 @@ heal_erased_bytewise_kernel<P>, hrs_heal_erased.hip): seven stripes of two
 windows plus a tail, each with its own erasure pattern, survivor errors within
 capacity planted at window, piece and row edges. Expected bytes are the
 oracle-encoded stripes themselves and the reports are counted from the planted
-list; at parity_size 8, where the reference locator leaves a few columns
-within capacity unresolved, the byte-exact reference is hrs_heal_erased_host.
+list; at parity_size 5 to 8, where the reference locator may leave a few
+columns within capacity unresolved, the byte-exact reference is
+hrs_heal_erased_host.
 The CPU test at the top checks the inputs without a device."""
 import random
 
@@ -15,7 +16,7 @@ import heal_erased_inputs as H
 from lambdafs_amd import HipReedSolomonCode, HrsError, TooManyErasedLocations, _lib, device
 
 L = 2 * H.WINDOW + 33
-SHAPES = [(10, 4), (12, 4), (6, 3), (3, 2), (4, 1), (20, 8)]
+SHAPES = [(10, 4), (12, 4), (6, 3), (3, 2), (4, 1), (20, 8), (6, 5), (7, 6), (10, 7)]
 NONE_DEV = -2  # HRS_DEVICE_NONE
 SPARE = 3
 
@@ -57,7 +58,7 @@ def _unresolved_share(k, p, bad, clean, pats, planted):
 def test_inputs_within_capacity(k, p):
     """No device: the patterns cover what the issue lists, the planted errors
     are within capacity, and hrs_heal_erased_host restores them: all of them
-    and with exactly the planted reports at p <= 4; at p = 8 all but the
+    and with exactly the planted reports at p <= 4; at p > 4 all but the
     unresolved columns, which stay below 5 % of the planted ones."""
     n = k + p
     clean, bad, pats, planted = _case(k, p)
@@ -194,7 +195,7 @@ def test_clean_survivors_give_the_batch_repair_rows(cuda, k, p):
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("mode", [0, 2])
-@pytest.mark.parametrize("k,p", [(10, 4), (6, 3), (20, 8)])
+@pytest.mark.parametrize("k,p", [(10, 4), (6, 3), (20, 8), (6, 5), (7, 6), (10, 7)])
 def test_one_past_capacity_matches_the_host(cuda, k, p, mode):
     n = k + p
     clean, bad, pats, planted = _case(k, p, over=1, seed=4)

@@ -3,7 +3,7 @@ hrs_heal_erased_crc.hip, and the two-pass route): the inputs of
 tests/heal_erased_inputs.py as they stand, seven stripes with seven erasure
 patterns and survivor errors planted at window, piece and row edges. Expected
 bytes are the oracle-encoded stripes and the reports the counts of the planted
-list (parity_size 8: hrs_heal_erased_host, byte for byte); every expected CRC
+list (parity_size above 4: hrs_heal_erased_host, byte for byte); every expected CRC
 is zlib.crc32 over the expected bytes, continued from the crc_in word. L = 4096
 is the fused shape (kernel mode 3 pins the fused kernel, mode 2 the byte-granular
 one, mode 0 takes what was measured faster), L = 4096 + 100 adds a row tail and
@@ -20,7 +20,7 @@ from test_gpu_scrub_crc import crcs_of
 
 pytestmark = pytest.mark.gpu
 
-SHAPES = [(10, 4), (12, 4), (6, 3), (3, 2), (4, 1), (20, 8), (247, 8)]
+SHAPES = [(10, 4), (12, 4), (6, 3), (3, 2), (4, 1), (20, 8), (247, 8), (6, 5), (7, 6), (10, 7)]
 LENGTHS = [2 * H.WINDOW, 2 * H.WINDOW + 100]
 NONE_DEV = -2  # HRS_DEVICE_NONE
 S = 7

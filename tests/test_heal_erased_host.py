@@ -177,7 +177,7 @@ def _call(code, stripe, erased):
     return np.stack(rows), [int(x) for x in rep]
 
 
-SHAPES = [(10, 4), (6, 3), (3, 2), (20, 8)]
+SHAPES = [(10, 4), (6, 3), (3, 2), (20, 8), (6, 5), (7, 6), (10, 7)]
 
 
 @pytest.mark.parametrize("k,p", SHAPES)
