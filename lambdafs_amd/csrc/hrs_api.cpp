@@ -7,7 +7,8 @@
 // Matrices are derived in closed form here; the CPU restatement of the
 // reference's per-byte loops lives only in oracle/ (test infrastructure).
 // Lifecycle, queries and matrices; the coding calls live in hrs_dispatch.cpp
-// (device batches), hrs_hostpath.cpp (host buffers) and hrs_batch_api.cpp.
+// (device batches), hrs_hostpath.cpp (host buffers), hrs_batch_api.cpp
+// (repair batches) and hrs_hostbatch_api.cpp (host-memory batches).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>

@@ -1,5 +1,6 @@
 // Internal interface shared by libhrs's host translation units (hrs_api.cpp,
-// hrs_matrix.cpp, hrs_dispatch.cpp, hrs_hostpath.cpp, hrs_batch_api.cpp): the
+// hrs_matrix.cpp, hrs_dispatch.cpp, hrs_hostpath.cpp, hrs_batch_api.cpp,
+// hrs_hostbatch_api.cpp): the
 // codec handle behind the C ABI's opaque hrs_codec, error reporting, and the
 // functions one unit calls in another. Not part of the ABI (hidden symbols).
 #pragma once
@@ -173,7 +174,7 @@ struct DeviceGuard {
 
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
-// ---- zero copy (hrs_batch_api.cpp): kernels read and write pinned host
+// ---- zero copy (hrs_hostbatch_api.cpp): kernels read and write pinned host
 // memory across the host link directly instead of H2D -> kernel -> D2H — the
 // link then carries both directions at once with no copy-engine calls
 // (profiles/r04/NOTES.md). HRS_ZEROCOPY=0 turns it off (A/B runs; read per
@@ -349,15 +350,70 @@ hrs_status repair_args_ok(hrs_codec* c, const uint8_t* const* rows, const uint32
                           const uint32_t* verdicts, const uint32_t* crc_out, bool* empty);
 
 // ---- per-call device tables (hrs_batch_api.cpp)
-// The next of the handle's two batch slots (pinned staging `host` + device
-// buffer `dev`, each at least `need` bytes), waited idle. The caller fills
-// host, copies it to dev on its stream, and after its launches records
-// slot->done there and sets slot->pending.
-hrs_status batch_slot_acquire(hrs_codec* c, size_t need, hrs_codec::BatchSlot** slot);
+// Two byte ranges, a table and the per-stripe indices into it, through the
+// next of the handle's two batch slots (pinned staging + device buffer, waited
+// idle) and up to the device on s: the table at (*slot)->dev, the indices
+// a_bytes after it. After its launches the caller calls slot_used, on every
+// exit: the slot's table may be in use whether or not every launch went out.
+hrs_status upload(hrs_codec* c, const void* a, size_t a_bytes, const void* b, size_t b_bytes, hipStream_t s,
+                  hrs_codec::BatchSlot** slot);
+void slot_used(hrs_codec::BatchSlot* sl, hipStream_t s);
+
+// ---- repair batches (hrs_batch_api.cpp)
+// The plans of a heterogeneous repair batch: one per distinct erasure
+// pattern (its live survivor locations and packed coefficients), the pattern
+// index of every stripe, and each pattern's full ne x n matrix (for the
+// per-stripe fallback when a pattern exceeds the batch kernel's shape).
+struct BatchPlanSet {
+  std::vector<hrs::BatchPlan> plans;
+  std::vector<int32_t> pat;
+  std::vector<std::vector<uint8_t>> mats;
+  bool fused = true;  // every pattern fits one batch_bitsliced launch
+  int max_nout = 0, max_nin = 0;
+  // the device copies (upload_plans; pat indexed by the absolute stripe number) and their slot
+  const hrs::BatchPlan* dplans = nullptr;
+  const int32_t* dpat = nullptr;
+  hrs_codec::BatchSlot* slot = nullptr;
+};
+hrs_status build_batch_plans(hrs_codec* c, const int* erased, int max_erased, size_t nstripes, BatchPlanSet& ps);
+hrs_status upload_plans(hrs_codec* c, BatchPlanSet& ps, hipStream_t s);
+// Where a batch lies: stripe i's row l at stripes + i * stripe_stride +
+// l * row_stride, its output t at out + i * out_stripe_stride + t * out_row_stride.
+struct BatchGeom {
+  const uint8_t* stripes;
+  size_t row_stride, stripe_stride;
+  uint8_t* out;
+  size_t out_row_stride, out_stripe_stride;
+  size_t len;
+};
+// The CRC-32s of a repair batch (DEVICE arrays at the range's first stripe):
+// out[i * max_erased + t] continues in[...] (NULL = fresh) over output t of
+// stripe i, and over no bytes for t past the stripe's losses.
+struct BatchCrcs {
+  int max_erased;
+  const uint32_t* in;
+  uint32_t* out;
+};
+// Repairs stripes [s0, s0 + ns) of a batch on stream s; g points at stripe s0.
+// crc != NULL: with their CRCs, through the handle's raw-CRC scratch (taken and
+// released on s); the plans must have been uploaded. Without CRCs they must
+// have been when ps.fused (else: one run_apply per stripe).
+hrs_status run_batch(hrs_codec* c, const BatchPlanSet& ps, const BatchGeom& g, size_t s0, size_t ns,
+                     const BatchCrcs* crc, hipStream_t s);
+// The argument rules of the decode-batch entry points, in this order: the
+// handle (NULL: HRS_EINVAL, no message), the argument block, the empty batch
+// (*empty = true: return HRS_OK and touch nothing), nstripes < 2^31 unless
+// kBatchDeviceSet (the members check their ranges), then with kBatchWithCrc
+// crc_args_ok over nstripes * max_erased words. The device is the caller's.
+enum : unsigned { kBatchWithCrc = 1u, kBatchDeviceSet = 2u };
+hrs_status decode_batch_args_ok(hrs_codec* c, const BatchGeom& g, const int* erased, int max_erased, size_t nstripes,
+                                unsigned flags, const uint32_t* crc_in, const uint32_t* crc_out, bool* empty);
 
 // ---- shared by the CRC entry points
 // crc_out may be crc_in itself; any other overlap of the two n-word arrays is refused (hrs_batch_api.cpp).
 bool crc_arrays_apart(const uint32_t* crc_in, const uint32_t* crc_out, size_t n);
+// crc_out not NULL and crc_arrays_apart, or HRS_EINVAL (hrs_batch_api.cpp).
+hrs_status crc_args_ok(hrs_codec* c, const uint32_t* crc_in, const uint32_t* crc_out, size_t n);
 // The fold alone (hrs_dispatch.cpp): raw window CRCs of nsr (stripe, row)
 // pairs, windows of `win` bytes, into crc_out, continuing crc_in.
 hrs_status crc_fold_windows(hrs_codec* c, size_t len, uint64_t nsr, const uint32_t* crc_in, uint32_t* crc_out,

@@ -8,7 +8,7 @@
 // healed on the CPU (hrs_heal_host, hrs_heal_erased_host), the kernels'
 // byte-exact reference; also hrs_repair_checked_host, checked repair of one
 // stripe over those same CPU pieces (its device call is hrs_repair_api.cpp).
-// The host-memory batches are in hrs_batch_api.cpp beside the pipeline they
+// The host-memory batches are in hrs_hostbatch_api.cpp beside the pipeline they
 // share. The per-column algorithm is hrs_locator.hpp, the same code the
 // kernels run.
 //
@@ -366,29 +366,17 @@ hrs_status erased_sets(hrs_codec* c, const int* erased, int max_erased, size_t n
 namespace {
 
 // The pattern table and the pattern indices of `nstripes` stripes into the
-// next batch slot and up to the device on s. The caller records the slot's
-// event after its launches (slot_used).
-hrs_status upload_patterns(hrs_codec* c, const std::vector<hrs::ErasePattern>& pats, const int32_t* pat,
-                           size_t nstripes, hipStream_t s, hrs_codec::BatchSlot** slot,
-                           const hrs::ErasePattern** dpats, const int32_t** dpat) {
+// next batch slot and up to the device on s (upload). The caller calls
+// slot_used after its launches.
+hrs_status pattern_table(hrs_codec* c, const std::vector<hrs::ErasePattern>& pats, const int32_t* pat, size_t nstripes,
+                         hipStream_t s, hrs_codec::BatchSlot** slot, const hrs::ErasePattern** dpats,
+                         const int32_t** dpat) {
   const size_t pat_bytes = pats.size() * sizeof(hrs::ErasePattern);
-  const size_t need = pat_bytes + nstripes * sizeof(int32_t);
-  hrs_status st = batch_slot_acquire(c, need, slot);
+  const hrs_status st = upload(c, pats.data(), pat_bytes, pat, nstripes * sizeof(int32_t), s, slot);
   if (st != HRS_OK) return st;
-  hrs_codec::BatchSlot* sl = *slot;
-  std::memcpy(sl->host, pats.data(), pat_bytes);
-  std::memcpy(sl->host + pat_bytes, pat, nstripes * sizeof(int32_t));
-  const hipError_t e = hipMemcpyAsync(sl->dev, sl->host, need, hipMemcpyHostToDevice, s);
-  if (e != hipSuccess) return hip_fail(c, e, "hipMemcpyAsync patterns");
-  *dpats = reinterpret_cast<const hrs::ErasePattern*>(sl->dev);
-  *dpat = reinterpret_cast<const int32_t*>(sl->dev + pat_bytes);
+  *dpats = reinterpret_cast<const hrs::ErasePattern*>((*slot)->dev);
+  *dpat = reinterpret_cast<const int32_t*>((*slot)->dev + pat_bytes);
   return HRS_OK;
-}
-
-// the slot's table may be in use whether or not every launch went out
-void slot_used(hrs_codec::BatchSlot* sl, hipStream_t s) {
-  if (hipEventRecord(sl->done, s) == hipSuccess) sl->pending = true;
-  else (void)hipStreamSynchronize(s);
 }
 
 }  // namespace
@@ -398,7 +386,7 @@ hrs_status run_heal_erased(hrs_codec* c, uint8_t* const* rows, size_t stride, si
                            size_t report_stride, hipStream_t s) {
   hrs_codec::BatchSlot* sl = nullptr;
   hrs::HealErasedArgs a{};
-  hrs_status st = upload_patterns(c, pats, pat, nstripes, s, &sl, &a.pats, &a.pat);
+  hrs_status st = pattern_table(c, pats, pat, nstripes, s, &sl, &a.pats, &a.pat);
   if (st != HRS_OK) return st;
   st = run_windows_tail(
       c, a.s, rows, stride, len, nstripes, reports, report_stride, s, "heal erased",
@@ -450,7 +438,7 @@ hrs_status run_heal_erased_crc(hrs_codec* c, uint8_t* const* rows, size_t stride
   a.c.p = c->p;
   a.c.tables = c->crc_tables_a;
   hrs_codec::BatchSlot* sl = nullptr;
-  st = upload_patterns(c, pats, pat, nstripes, s, &sl, &a.pats, &a.pat);
+  st = pattern_table(c, pats, pat, nstripes, s, &sl, &a.pats, &a.pat);
   if (st != HRS_OK) return st;
   // scratch: the raw window CRCs, then the dirty-task count and list
   const size_t raw_bytes = (a.c.ntasks * static_cast<size_t>(n) * 4 + 7) & ~static_cast<size_t>(7);
