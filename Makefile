@@ -69,7 +69,7 @@ build/hrs_probe.o: include/hrs_probe.h
 	    grep -E 'Function Name|VGPRs:|SGPRs:|ScratchSize|Occupancy|LDS Size'
 
 KOBJ     := build/hrs_kernels.o build/hrs_runtime.o build/hrs_batch.o build/hrs_crc.o build/hrs_fused.o build/hrs_decode_crc.o \
-            build/hrs_batch_crc.o build/hrs_gate.o build/hrs_scrub.o build/hrs_scrub_crc.o build/hrs_heal_erased.o \
+            build/hrs_batch_crc.o build/hrs_scrub.o build/hrs_scrub_crc.o build/hrs_heal_erased.o \
             build/hrs_heal_erased_crc.o build/hrs_repair.o
 
 $(LIB): $(API_OBJ) $(KOBJ) lambdafs_amd/csrc/libhrs.map

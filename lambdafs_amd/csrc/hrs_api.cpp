@@ -187,25 +187,11 @@ void hrs_destroy(hrs_codec* c) {
     (void)hipEventDestroy(c->crc_raw_done);
   }
   if (c->crc_raw) (void)hipFree(c->crc_raw);
-  for (auto& h : c->host) {
-    if (h.stream) {
-      (void)hipStreamSynchronize(h.stream);
-      (void)hipStreamDestroy(h.stream);
-    }
-    if (h.done) (void)hipEventDestroy(h.done);
-    if (h.dev) (void)hipFree(h.dev);
-    if (h.pin) (void)hipHostFree(h.pin);
-  }
-  if (c->qflags) (void)hipHostFree(c->qflags);  // every slot stream has drained above
+  for (auto& h : c->host) free_stage_slot(h);
   for (auto& a : c->async) {
-    if (a.stream) {
-      (void)hipStreamSynchronize(a.stream);
-      (void)hipStreamDestroy(a.stream);
-    }
-    for (hipEvent_t e : {a.done, a.t_start, a.t_end})
+    free_stage_slot(a);
+    for (hipEvent_t e : {a.t_start, a.t_end})
       if (e) (void)hipEventDestroy(e);
-    if (a.dev) (void)hipFree(a.dev);
-    if (a.pin) (void)hipHostFree(a.pin);
   }
   for (hipStream_t s : {c->hbatch_in, c->hbatch_out})
     if (s) (void)hipStreamSynchronize(s);

@@ -8,7 +8,6 @@
 
 #include <cstdint>
 #include <map>
-#include <set>
 #include <string>
 #include <vector>
 
@@ -69,24 +68,20 @@ struct hrs_codec {
     bool pending = false;
   } batch[2];
   int batch_next = 0;
-  // host-buffer calls: chunk slots (8 by default, HRS_HOST_SLOTS 2-8),
-  // each pinned staging + device rows + its own stream; a slot is reused once
-  // its D2H event has completed
-  struct HostSlot {
+  // host-buffer calls (hrs_hostpath.cpp): a staging slot is pinned staging,
+  // device rows of the same size and its own stream, with the event recorded
+  // after the work queued on it (stage_slot sizes one, free_stage_slot frees it)
+  struct StageSlot {
     uint8_t* pin = nullptr;
     uint8_t* pin_dev = nullptr;  // device address of `pin` (zero-copy kernels)
     uint8_t* dev = nullptr;
     size_t bytes = 0;
     hipStream_t stream = nullptr;
     hipEvent_t done = nullptr;
-  } host[hrs::kHostSlots];
-  // gated staged pipeline (hrs_hostpath.cpp staged_run): coherent pinned
-  // ready / done / miss words, the next chunk tag, the gates' timeout in
-  // wall-clock ticks, and the chunk shapes (CRC mode, length) run before
-  uint32_t* qflags = nullptr;
-  uint32_t qtag = 0;
-  uint64_t gate_timeout = 0;
-  std::set<uint64_t> staged_shapes;
+  };
+  // synchronous calls: the chunk slots (8 by default, HRS_HOST_SLOTS 2-8); a
+  // slot is reused once its chunk's event has completed
+  StageSlot host[hrs::kHostSlots];
   std::map<uint64_t, std::vector<uint32_t>> crc_ztabs;  // Z_n as 4 x 256 tables, by n (host folds)
   // host-memory batches (hrs_*_batch_host): a ring of chunk slots, each a
   // device image + output block, pinned staging (pageable callers only) and
@@ -116,15 +111,9 @@ struct hrs_codec {
   hipStream_t hbatch_in = nullptr;   // H2D of every host-batch slot
   hipStream_t hbatch_out = nullptr;  // D2H of every host-batch slot
   // asynchronous host-buffer calls (hrs_*_submit / hrs_collect): a ring of
-  // operation slots, each pinned staging + device rows + its own stream; an
+  // operation slots, each a staging slot plus the state of its ticket; an
   // operation occupies its slot from submit until it is collected
-  struct AsyncSlot {
-    uint8_t* pin = nullptr;
-    uint8_t* pin_dev = nullptr;  // device address of `pin` (zero-copy kernels)
-    uint8_t* dev = nullptr;
-    size_t bytes = 0;
-    hipStream_t stream = nullptr;
-    hipEvent_t done = nullptr;
+  struct AsyncSlot : StageSlot {
     hipEvent_t t_start = nullptr;  // timing events (hrs_set_timing)
     hipEvent_t t_end = nullptr;
     bool timed = false;   // this operation recorded t_start / t_end
@@ -194,6 +183,9 @@ bool host_device_ptr(const void* p, size_t len, uint8_t** dp);
 hrs::CopyPool& copy_pool(hrs_codec* c);
 // How copy-ins store into pinned staging (hrs::kStore*; HRS_HOST_NT).
 uint8_t host_store_mode();
+// Drains a staging slot's stream and frees everything the slot holds
+// (hrs_hostpath.cpp; hrs_destroy).
+void free_stage_slot(hrs_codec::StageSlot& h);
 
 // The compile-time encode kernels hold the hops RS generator (rs) or the
 // ISA-L Cauchy rows (nrs) of a (k, p) shape; only those families' G may take

@@ -127,12 +127,6 @@ hipError_t launch_scrub_bytewise(const ScrubArgs& a, hipStream_t s);
 hipError_t launch_heal(const ScrubArgs& a, hipStream_t s);
 hipError_t launch_heal_bytewise(const ScrubArgs& a, hipStream_t s);
 
-// ---- stream gates of the queued host pipeline (hrs_gate.hip)
-// gate: waits until *ready (a coherent pinned word the host writes) reaches
-// `want` (serial-number order), or `timeout` wall-clock ticks pass (then *fail
-// = 1). signal: *done = tag with a system-scope release.
-hipError_t launch_gate(const uint32_t* ready, uint32_t want, uint32_t* fail, uint64_t timeout, hipStream_t s);
-hipError_t launch_signal(uint32_t* done, uint32_t tag, hipStream_t s);
 hipError_t launch_batch_bytewise(const BatchArgs& a, hipStream_t s);
 
 }  // namespace hrs

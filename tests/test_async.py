@@ -98,6 +98,42 @@ def test_decode_rounds_out_of_order_vs_oracle(cuda):
             code.collect(t, out)
 
 
+@pytest.mark.parametrize("L", [1, 2048, 4096 + 5])
+@pytest.mark.parametrize("k,p", [(10, 4), (6, 3)])
+def test_small_checksummed_rounds_out_of_order(cuda, k, p, L):
+    """The submit's cell at the sizes where its path changes: below a CRC
+    window, exactly one window, and a ragged cell (no one-pass CRC kernel, so
+    it takes the copy engine even with zero copy on). One checksummed encode
+    round and one checksummed two-erasure decode round in flight, the decode
+    collected first; outputs vs the oracle, CRCs vs zlib chained from non-zero
+    running values."""
+    n = k + p
+    code = HipReedSolomonCode(k, p, device=0, zero_inputs_after_encode=False)
+    rng = np.random.default_rng(1000 * k + L)
+    data = [rng.integers(0, 256, L, dtype=np.uint8) for _ in range(k)]
+    par = C.encode_bulk(k, p, [d.copy() for d in data])
+    stripe = list(par) + data
+    lost = [p + 1, 0]
+    tr, ntr = _decoder_sets(k, p, lost)
+    rows = [None if x in ntr else stripe[x].copy() for x in range(n)]
+    reads = [np.zeros(L, np.uint8) if r is None else r.copy() for r in rows]
+    want = C.decode_bulk5(k, p, reads, lost, tr, ntr)
+    te = code.encodeBulkAsync([d.copy() for d in data], checksums=True)
+    td = code.decodeBulkAsync(rows, lost, tr, ntr, checksums=True)
+    assert code.pending() == 2
+    run_d = [int(v) for v in rng.integers(1, 1 << 32, len(lost), dtype=np.uint64)]
+    out = [np.full(L, 0xEE, np.uint8) for _ in lost]
+    crcs = code.collect(td, out, run_d)
+    assert all(np.array_equal(out[i], want[i]) for i in range(len(lost)))
+    assert crcs == [zlib.crc32(want[i].tobytes(), run_d[i]) for i in range(len(lost))]
+    run_e = [int(v) for v in rng.integers(1, 1 << 32, n, dtype=np.uint64)]
+    out = [np.full(L, 0xEE, np.uint8) for _ in range(p)]
+    crcs = code.collect(te, out, run_e)
+    assert all(np.array_equal(out[o], par[o]) for o in range(p))
+    assert crcs == [zlib.crc32(b.tobytes(), run_e[i]) for i, b in enumerate(data + list(par))]
+    assert code.pending() == 0
+
+
 def test_async_argument_errors(cuda):
     torch = cuda
     k, p, L = 10, 4, 4096

@@ -25,34 +25,28 @@ def test_host_crc_exported():
     assert hasattr(L, "hrs_encode_crc") and hasattr(L, "hrs_decode_crc")
 
 
-@pytest.fixture(params=["zero_copy", "copy_engine", "gated", "wide_chunks"])
+@pytest.fixture(params=["zero_copy", "copy_engine", "small_chunks", "wide_chunks"])
 def transfer_mode(request, monkeypatch):
     """Every test runs each way the synchronous host-buffer calls can move
     bytes: the staged zero-copy path (the default: rows copied into pinned
     staging, the kernel works on the staging across the link) and the copy
-    engine (HRS_ZEROCOPY=0: pinned staging, H2D, kernel, D2H), and the gated
-    queue (HRS_HOST_GATE=1, 128 KiB chunks after a 64 KiB first one over 4
-    slots: every chunk's kernels queued ahead behind gate kernels the host
-    opens after each copy-in), and 512 KiB chunks over 2 slots (wide_chunks:
-    the 1,024-thread fused encode + CRC blocks). Which caller memory runs in place
+    engine (HRS_ZEROCOPY=0: pinned staging, H2D, kernel, D2H), and small
+    chunks (small_chunks: 128 KiB chunks after a 64 KiB first one over 4
+    slots, so every slot is reused several times), and 512 KiB chunks over 2
+    slots (wide_chunks: the 1,024-thread fused encode + CRC blocks). Which caller memory runs in place
     (runtime-pinned only) is test_host_memory.py."""
     monkeypatch.delenv("HRS_ZEROCOPY", raising=False)
-    for var in ("HRS_HOST_GATE", "HRS_HOST_CHUNK", "HRS_HOST_SLOTS", "HRS_HOST_FIRST"):
+    for var in ("HRS_HOST_CHUNK", "HRS_HOST_SLOTS", "HRS_HOST_FIRST"):
         monkeypatch.delenv(var, raising=False)
     if request.param == "copy_engine":
         monkeypatch.setenv("HRS_ZEROCOPY", "0")
-        monkeypatch.setenv("HRS_HOST_GATE", "0")
-    elif request.param == "gated":  # gated queued chunks, small and many (hrs_hostpath.cpp staged_run)
-        monkeypatch.setenv("HRS_HOST_GATE", "1")
+    elif request.param == "small_chunks":  # small and many (hrs_hostpath.cpp staged_run)
         monkeypatch.setenv("HRS_HOST_CHUNK", "131072")
         monkeypatch.setenv("HRS_HOST_SLOTS", "4")
         monkeypatch.setenv("HRS_HOST_FIRST", "65536")
     elif request.param == "wide_chunks":  # 512 KiB x 2 slots (round 5's default)
-        monkeypatch.setenv("HRS_HOST_GATE", "0")
         monkeypatch.setenv("HRS_HOST_CHUNK", "524288")
         monkeypatch.setenv("HRS_HOST_SLOTS", "2")
-    else:
-        monkeypatch.setenv("HRS_HOST_GATE", "0")
     return request.param
 
 

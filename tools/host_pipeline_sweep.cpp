@@ -1,15 +1,14 @@
 // A/B sweep of the staged synchronous host-buffer pipeline's knobs
 // (hrs_hostpath.cpp staged_run: HRS_HOST_CHUNK, HRS_HOST_SLOTS,
-// HRS_HOST_FIRST, HRS_HOST_GATE, HRS_HOST_NT, HRS_HOST_FOLD, all read per call), interleaved
-// round by
-// round in one process over the four calls the JNI shim makes per Encoder /
+// HRS_HOST_FIRST, HRS_HOST_NT, HRS_HOST_FOLD, all read per call), interleaved
+// round by round in one process over the four calls the JNI shim makes per Encoder /
 // Decoder round: hrs_encode / hrs_decode / hrs_encode_crc / hrs_decode_crc on
 // one RS(k,p) stripe of L-byte pageable rows (default RS(10,4), 1 MiB).
 // Every variant's parity, CRCs and repaired row must equal the first
 // variant's (and the repaired row the lost one), or the tool fails.
 // ROWS=pinned in a variant's environment runs it on a hipHostMalloc'd copy of
 // the rows (the in-place path).
-// Usage: host_pipeline_sweep [calls] [rounds] [L] [name:chunk:slots:first:gate[:nt[:fold[:K=V+K=V]]],...]
+// Usage: host_pipeline_sweep [calls] [rounds] [L] [name:chunk:slots:first[:nt[:fold[:K=V+K=V]]],...]
 //   (one JSON line per variant, medians)
 #include <algorithm>
 #include <chrono>
@@ -26,16 +25,14 @@
 #include "../include/hrs.h"
 
 struct Variant {
-  std::string name, chunk, slots, first, gate, nt = "0", fold = "1";
+  std::string name, chunk, slots, first, nt = "0", fold = "1";
   std::string extra;  // more environment for this variant: KEY=VAL+KEY=VAL (unset for the others)
 };
 
-// Default variants; argv[4] may list others as name:chunk:slots:first:gate,...
+// Default variants; argv[4] may list others as name:chunk:slots:first,...
 static std::vector<Variant> default_variants() {
-  return {{"c512_s2", "524288", "2", "0", "0"},      {"c256_s4", "262144", "4", "0", "0"},
-          {"c128_s4", "131072", "4", "0", "0"},      {"c128_s8", "131072", "8", "0", "0"},
-          {"c512_s2_gate", "524288", "2", "0", "1"}, {"c256_s2_gate", "262144", "2", "0", "1"},
-          {"c256_s4_gate", "262144", "4", "0", "1"}, {"c128_s4_gate", "131072", "4", "0", "1"}};
+  return {{"c512_s2", "524288", "2", "0"}, {"c256_s4", "262144", "4", "0"},
+          {"c128_s4", "131072", "4", "0"}, {"c128_s8", "131072", "8", "0"}};
 }
 
 static std::vector<Variant> parse_variants(const char* spec) {
@@ -45,14 +42,14 @@ static std::vector<Variant> parse_variants(const char* spec) {
   while (pos < s.size()) {
     size_t end = s.find(',', pos);
     if (end == std::string::npos) end = s.size();
-    std::string item = s.substr(pos, end - pos), f[8] = {"", "", "", "", "", "0", "1", ""};
+    std::string item = s.substr(pos, end - pos), f[7] = {"", "", "", "", "0", "1", ""};
     size_t q = 0;
-    for (int i = 0; i < 8 && q < item.size(); ++i) {
+    for (int i = 0; i < 7 && q < item.size(); ++i) {
       size_t c = item.find(':', q);
       f[i] = item.substr(q, c == std::string::npos ? std::string::npos : c - q);
       q = c == std::string::npos ? item.size() : c + 1;
     }
-    v.push_back({f[0], f[1], f[2], f[3], f[4], f[5], f[6], f[7]});
+    v.push_back({f[0], f[1], f[2], f[3], f[4], f[5], f[6]});
     pos = end + 1;
   }
   return v;
@@ -151,7 +148,6 @@ int main(int argc, char** argv) {
       setenv("HRS_HOST_CHUNK", V.chunk.c_str(), 1);
       setenv("HRS_HOST_SLOTS", V.slots.c_str(), 1);
       setenv("HRS_HOST_FIRST", V.first.c_str(), 1);
-      setenv("HRS_HOST_GATE", V.gate.c_str(), 1);
       setenv("HRS_HOST_NT", V.nt.c_str(), 1);
       setenv("HRS_HOST_FOLD", V.fold.c_str(), 1);
       for (const Variant& o : kVariants)  // other variants' extra keys unset, then this one's set
@@ -202,11 +198,12 @@ int main(int argc, char** argv) {
     return v[v.size() / 2];
   };
   for (int v = 0; v < nv; ++v)
-    printf("{\"variant\": \"%s\", \"chunk\": %s, \"slots\": %s, \"first\": %s, \"gate\": %s, \"nt\": \"%s\", \"path\": \"%s\", "
+    printf("{\"variant\": \"%s\", \"chunk\": %s, \"slots\": %s, \"first\": %s, \"nt\": \"%s\", \"path\": \"%s\", "
            "\"L\": %zu, \"calls\": %d, \"rounds\": %d, \"encode_ms\": %.4f, \"decode_ms\": %.4f, \"encode_crc_ms\": %.4f, "
            "\"decode_crc_ms\": %.4f, \"ok\": %s}\n",
            kVariants[v].name.c_str(), kVariants[v].chunk.c_str(), kVariants[v].slots.c_str(), kVariants[v].first.c_str(),
-           kVariants[v].gate.c_str(), kVariants[v].nt.c_str(), paths[v].c_str(), L, calls, rounds, med(t[v * 4]), med(t[v * 4 + 1]), med(t[v * 4 + 2]), med(t[v * 4 + 3]),
+           kVariants[v].nt.c_str(), paths[v].c_str(), L, calls, rounds, med(t[v * 4]), med(t[v * 4 + 1]),
+           med(t[v * 4 + 2]), med(t[v * 4 + 3]),
            ok ? "true" : "false");
   hrs_destroy(c);
   return ok ? 0 : 1;
