@@ -176,7 +176,7 @@ BATCH = (
     ])
 )
 
-# hrs_encode_crc_dev, RS(10,4) mode 3. cfg = (stripes, with crc_in)
+# hrs_encode_crc_dev, RS(10,4) mode 3. cfg = (stripes, with crc_in[, (code, k, p, kernel mode)])
 ENCODE_CRC = [
     Case("encode_crc", "encode_crc", cfg, L, place, kernel) for cfg, L, place, kernel in [
         ((3, False), 2048, "aligned", "encode_crc*"),
@@ -188,6 +188,8 @@ ENCODE_CRC = [
         ((3, False), 2049, "shift", BYTEWISE),
         ((3, True), 2048, "shift", BYTEWISE),
         ((3, True), 2048, "pad5", BYTEWISE),
+        # a (k, p) inside kFusedMaxK / kFusedMaxP that no fused kernel is built for: two passes on whole windows
+        ((3, False, ("rs", 5, 2, 0)), 2048, "aligned", "bitsliced_pipe_kernel<2, 8>"),
     ]
 ]
 
@@ -203,6 +205,8 @@ DECODE_CRC = [
         (((5,), False), 2048, "shift", BYTEWISE),
         (((5,), True), 2049, "shift", BYTEWISE),
         (((0, 13), True), 2048, "pad5", BYTEWISE),
+        # 4 outputs from 10 live inputs, more than the 8 the fused repair takes: two passes on whole windows
+        (((0, 5, 9, 13), False), 2048, "aligned", "bitsliced_kernel<4, 12>"),
     ]
 ]
 
@@ -449,15 +453,15 @@ def _crc_words(rows, crc_in):
 @pytest.mark.parametrize("case", ENCODE_CRC, ids=_id)
 def test_encode_crc_footprint(cuda, case):
     torch = cuda
-    k, p = 10, 4
-    S, with_in = case.cfg
+    S, with_in = case.cfg[:2]
+    kind, k, p, mode = case.cfg[2] if len(case.cfg) > 2 else ("rs", 10, 4, 3)
     arena = _arena(S, case.L, case.place, seed=case.L)
     dnames = arena.add_rows("data", k, "input")
     pnames = arena.add_rows("parity", p, "output")
-    want = _encode_outputs(arena, "rs", k, p, dnames, pnames)
+    want = _encode_outputs(arena, kind, k, p, dnames, pnames)
     crcs = CrcArena(S, k + p, with_in, seed=case.L)
     words = _crc_words([arena.pre(x) for x in dnames] + [want[x] for x in pnames], crcs.crc_in())
-    code = _make_code("rs", k, p, 3)
+    code = _make_code(kind, k, p, mode)
     flat, v = arena.to_device()
     cflat, cin, cout = crcs.to_device()
     code._check(_lib.lib().hrs_encode_crc_dev(code._handle(), _ptrs(v, dnames), _stride(arena), _ptrs(v, pnames),
