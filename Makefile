@@ -16,9 +16,9 @@ HDRS     := Makefile include/hrs.h lambdafs_amd/csrc/hrs_device.hpp lambdafs_amd
             lambdafs_amd/csrc/hrs_scrub_device.hpp lambdafs_amd/csrc/hrs_repair.hpp lambdafs_amd/csrc/hrs_repair_rule.hpp
 
 # Host translation units of the C ABI (no kernels): lifecycle + queries,
-# matrices, device dispatch + CRC, host-buffer path, repair batches,
-# host-memory batches, scrubbing, checked repair.
-API_SRC  := hrs_api hrs_matrix hrs_dispatch hrs_hostpath hrs_batch_api hrs_hostbatch_api hrs_scrub_api hrs_repair_api
+# matrices, device dispatch, the CRC-32 service, host-buffer path, repair
+# batches, host-memory batches, scrubbing, checked repair.
+API_SRC  := hrs_api hrs_matrix hrs_dispatch hrs_crc_api hrs_hostpath hrs_batch_api hrs_hostbatch_api hrs_scrub_api hrs_repair_api
 API_OBJ  := $(patsubst %,build/%.o,$(API_SRC))
 
 JNI      := lambdafs_amd/libhrs_jni.so

@@ -178,12 +178,13 @@ hrs_status launch_batch(hrs_codec* c, const BatchPlanSet& ps, const BatchGeom& g
 hrs_status launch_batch_crc(hrs_codec* c, const BatchPlanSet& ps, const BatchGeom& g, size_t s0, size_t ns,
                             const BatchCrcs& crc, hipStream_t hs, uint32_t* raw) {
   const BatchCrcMask mask{ps.dplans, ps.dpat + s0, crc.max_erased};
+  auto fold = [&](uint64_t win) {
+    return crc_fold(c, g.len, ns * static_cast<uint64_t>(crc.max_erased), crc.in, crc.out, hs, raw, win, &mask);
+  };
   if (ps.max_nout == 0)  // nothing lost anywhere: every CRC continues over no bytes
-    return batch_crc_fold(c, g.len, ns, mask, crc.in, crc.out, hs, raw, hrs::kCrcWindow);
-  const bool one_pass = ps.fused && (c->kernel_mode == 0 || c->kernel_mode == 3) &&
-                        g.len % hrs::kWindowBytes == 0 && vector_aligned(g) && ps.max_nout <= 4 &&
-                        ps.max_nin <= (ps.max_nout == 4 ? 8 : 12);
-  if (one_pass) {
+    return fold(hrs::kCrcWindow);
+  // the one-pattern fused kernel's shapes at the batch's largest pattern
+  if (ps.fused && apply_crc_one_pass(c, ps.max_nout, ps.max_nin, g.len) && vector_aligned(g)) {
     hrs_status st = crc_window_tables(c);
     if (st != HRS_OK) return st;
     hrs::BatchCrcArgs d{};
@@ -196,7 +197,7 @@ hrs_status launch_batch_crc(hrs_codec* c, const BatchPlanSet& ps, const BatchGeo
     hipError_t e = hrs::launch_batch_decode_crc(d, ps.max_nout, ps.max_nin, hrs::device_cu_count(), hs);
     if (e != hipSuccess) return hip_fail(c, e, "batch decode+crc launch");
     c->last_kernel = hrs::last_kernel();
-    return batch_crc_fold(c, g.len, ns, mask, crc.in, crc.out, hs, raw, hrs::kWindowBytes);
+    return fold(hrs::kWindowBytes);
   }
   hrs_status st = launch_batch(c, ps, g, s0, ns, hs);
   if (st != HRS_OK) return st;
@@ -208,7 +209,7 @@ hrs_status launch_batch_crc(hrs_codec* c, const BatchPlanSet& ps, const BatchGeo
   }
   st = crc_windows(c, rows, strides, ps.max_nout, crc.max_erased, g.len, ns, hs, raw);
   if (st != HRS_OK) return st;
-  return batch_crc_fold(c, g.len, ns, mask, crc.in, crc.out, hs, raw, hrs::kCrcWindow);
+  return fold(hrs::kCrcWindow);
 }
 
 }  // namespace
@@ -216,9 +217,8 @@ hrs_status launch_batch_crc(hrs_codec* c, const BatchPlanSet& ps, const BatchGeo
 hrs_status run_batch(hrs_codec* c, const BatchPlanSet& ps, const BatchGeom& g, size_t s0, size_t ns,
                      const BatchCrcs* crc, hipStream_t s) {
   if (!crc) return launch_batch(c, ps, g, s0, ns, s);
-  const hrs_status st = crc_scratch(c, crc_raw_bytes_for(g.len, ns, crc->max_erased), s);
-  if (st != HRS_OK) return st;
-  return crc_scratch_release(c, s, launch_batch_crc(c, ps, g, s0, ns, *crc, s, c->crc_raw));
+  return with_crc_scratch(c, crc_raw_bytes_for(g.len, ns, crc->max_erased), s,
+                          [&] { return launch_batch_crc(c, ps, g, s0, ns, *crc, s, c->crc_raw); });
 }
 
 hrs_status upload(hrs_codec* c, const void* a, size_t a_bytes, const void* b, size_t b_bytes, hipStream_t s,

@@ -1,6 +1,6 @@
 // Internal interface shared by libhrs's host translation units (hrs_api.cpp,
-// hrs_matrix.cpp, hrs_dispatch.cpp, hrs_hostpath.cpp, hrs_batch_api.cpp,
-// hrs_hostbatch_api.cpp): the
+// hrs_matrix.cpp, hrs_dispatch.cpp, hrs_crc_api.cpp, hrs_hostpath.cpp,
+// hrs_batch_api.cpp, hrs_hostbatch_api.cpp): the
 // codec handle behind the C ABI's opaque hrs_codec, error reporting, and the
 // functions one unit calls in another. Not part of the ABI (hidden symbols).
 #pragma once
@@ -211,17 +211,36 @@ hrs_status decode5_matrix(hrs_codec* c, const int* erased, int ne, const int* nt
                           const int* to_read = nullptr, int nr = -1);
 void init_encode_matrix(hrs_codec* c);
 
-// ---- device dispatch + CRC (hrs_dispatch.cpp)
+// ---- device dispatch (hrs_dispatch.cpp)
 hrs_status run_apply(hrs_codec* c, const uint8_t* m, int nout, int nin, const uint8_t* const* in_rows,
                      size_t in_stride, uint8_t* const* out_rows, size_t out_stride, size_t len, size_t nstripes,
                      hipStream_t s, bool static_kp);
+
+// ---- CRC-32 (hrs_crc_api.cpp)
 size_t crc_raw_bytes_for(size_t len, size_t nstripes, int nrows);
 hrs_status run_crc(hrs_codec* c, const uint8_t* const* rows, const size_t* strides, int nrows, size_t len,
                    size_t nstripes, const uint32_t* crc_in, uint32_t* crc_out, hipStream_t s, uint32_t* raw);
 // The handle's raw-CRC scratch (c->crc_raw, at least `bytes`) for a call on
 // stream s, its uses chained by an event across streams; release records it.
+// with_crc_scratch is the only caller of the two and the only way to
+// c->crc_raw: it takes the scratch, runs `body` (hrs_status(); its launches go
+// on s) and releases on s with body's status, whether or not body succeeded.
+// A lease inside a lease (run_repair_checked around run_scrub_crc) asks for no
+// more than the outer one, so nothing is reallocated under it. A template, so
+// that the body is inlined into its caller.
 hrs_status crc_scratch(hrs_codec* c, size_t bytes, hipStream_t s);
 hrs_status crc_scratch_release(hrs_codec* c, hipStream_t s, hrs_status st);
+template <class Body>
+hrs_status with_crc_scratch(hrs_codec* c, size_t bytes, hipStream_t s, Body body) {
+  const hrs_status st = crc_scratch(c, bytes, s);
+  return st != HRS_OK ? st : crc_scratch_release(c, s, body());
+}
+// The CRC-32 of nrows rows of one stride after a pass that left them on
+// stream s (the stream orders that pass's stores before the window pass
+// reads them): a lease of crc_raw_bytes_for, then run_crc. The handle's last
+// kernel stays the pass's. crc_out[s * nrows + r].
+hrs_status crc_rows(hrs_codec* c, const uint8_t* const* rows, int nrows, size_t stride, size_t len, size_t nstripes,
+                    const uint32_t* crc_in, uint32_t* crc_out, hipStream_t s);
 hrs_status crc_window_tables(hrs_codec* c);  // c->crc_tables_a, uploaded once
 // The fold tables (kCrcLdsWordsB words, device) for rows of `len` bytes cut in
 // windows of `win` bytes, cached per handle; a caller with a fold kernel of its
@@ -232,16 +251,18 @@ hrs_status fold_tables_used(hrs_codec* c, hrs_codec::FoldTables* ft, hipStream_t
 // run_crc's window pass alone, raw rows laid out for a fold over nrows_total rows.
 hrs_status crc_windows(hrs_codec* c, const uint8_t* const* rows, const size_t* strides, int nrows, int nrows_total,
                        size_t len, size_t nstripes, hipStream_t s, uint32_t* raw);
-// The fold of a repair batch (windows of `win` bytes): output t of stripe s
-// past the stripe's losses (t >= plans[pat[s]].nout; device tables) yields
-// crc_in (0 when NULL) without reading raw. crc_out[s * rows_per_stripe + t].
+// The fold alone: raw window CRCs of nsr (stripe, row) pairs, windows of `win`
+// bytes, into crc_out, continuing crc_in. mask: the fold of a repair batch
+// (nsr = stripes * rows_per_stripe): output t of stripe s past the stripe's
+// losses (t >= plans[pat[s]].nout; device tables) yields crc_in (0 when NULL)
+// without reading raw. crc_out[s * rows_per_stripe + t].
 struct BatchCrcMask {
   const hrs::BatchPlan* plans;
   const int32_t* pat;
   int rows_per_stripe;
 };
-hrs_status batch_crc_fold(hrs_codec* c, size_t len, size_t nstripes, const BatchCrcMask& mask, const uint32_t* crc_in,
-                          uint32_t* crc_out, hipStream_t s, uint32_t* raw, uint64_t win);
+hrs_status crc_fold(hrs_codec* c, size_t len, uint64_t nsr, const uint32_t* crc_in, uint32_t* crc_out, hipStream_t s,
+                    uint32_t* raw, uint64_t win, const BatchCrcMask* mask = nullptr);
 // host_fold_win != NULL: when the fused one-pass kernel runs, no fold is
 // launched; the raw window CRCs stay in `raw` (layout [stripe][row][window])
 // and *host_fold_win receives the window size for the caller's host fold
@@ -406,10 +427,6 @@ hrs_status decode_batch_args_ok(hrs_codec* c, const BatchGeom& g, const int* era
 bool crc_arrays_apart(const uint32_t* crc_in, const uint32_t* crc_out, size_t n);
 // crc_out not NULL and crc_arrays_apart, or HRS_EINVAL (hrs_batch_api.cpp).
 hrs_status crc_args_ok(hrs_codec* c, const uint32_t* crc_in, const uint32_t* crc_out, size_t n);
-// The fold alone (hrs_dispatch.cpp): raw window CRCs of nsr (stripe, row)
-// pairs, windows of `win` bytes, into crc_out, continuing crc_in.
-hrs_status crc_fold_windows(hrs_codec* c, size_t len, uint64_t nsr, const uint32_t* crc_in, uint32_t* crc_out,
-                            hipStream_t s, uint32_t* raw, uint64_t win);
 
 }  // namespace hrs::api
 #pragma GCC visibility pop

@@ -629,11 +629,10 @@ hrs_status encode_batch_host_entry(hrs_codec* c, uint8_t* stripes, size_t row_st
       if (!crcs)
         return run_apply(c, c->g.data(), p, k, in.data(), img_stride, outp.data(), par_stride, len, ns, hs,
                          static_encode_family(c));
-      const hrs_status cs = crc_scratch(c, crc_raw_bytes_for(len, ns, c->n), hs);
-      if (cs != HRS_OK) return cs;
-      return crc_scratch_release(c, hs,
-                                 encode_crc_impl(c, in.data(), img_stride, outp.data(), par_stride, len, ns,
-                                                 crcs.in(s0 * n), crcs.out(s0 * n), hs, c->crc_raw));
+      return with_crc_scratch(c, crc_raw_bytes_for(len, ns, c->n), hs, [&] {
+        return encode_crc_impl(c, in.data(), img_stride, outp.data(), par_stride, len, ns, crcs.in(s0 * n),
+                               crcs.out(s0 * n), hs, c->crc_raw);
+      });
     };
     uint8_t* zs = nullptr;
     if (zero_copy_on() && host_device_ptr(stripes, span, &zs))  // the kernel works on the caller's stripes in place

@@ -43,9 +43,7 @@ hrs_status run_repair_checked(hrs_codec* c, uint8_t* const* rows, size_t stride,
   const size_t raw_bytes = round_up(crc_raw_bytes_for(len, nstripes, n) + 8, 256);  // either path of pass 1 fits
   const size_t list_bytes = round_up((1 + nstripes) * sizeof(uint32_t), 256);
   const size_t pats_bytes = nstripes * sizeof(hrs::ErasePattern);
-  st = crc_scratch(c, raw_bytes + list_bytes + pats_bytes, s);
-  if (st != HRS_OK) return st;
-  auto launches = [&]() -> hrs_status {
+  return with_crc_scratch(c, raw_bytes + list_bytes + pats_bytes, s, [&]() -> hrs_status {
     hrs_status r = run_scrub_crc(c, rows, stride, len, nstripes, reports, report_stride, nullptr, crc_out, s, false);
     if (r != HRS_OK) return r;
     const std::string kernel = c->last_kernel;  // hrs_last_kernel names pass 1's kernel
@@ -127,8 +125,7 @@ hrs_status run_repair_checked(hrs_codec* c, uint8_t* const* rows, size_t stride,
     if ((e = hrs::launch_repair_fold_verdict(fa, cus, s)) != hipSuccess) return hip_fail(c, e, "repair verdict launch");
     c->last_kernel = kernel;
     return fold_tables_used(c, ft, s);
-  };
-  return crc_scratch_release(c, s, launches());
+  });
 }
 
 }  // namespace

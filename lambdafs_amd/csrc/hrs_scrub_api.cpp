@@ -13,8 +13,8 @@
 // kernels run.
 //
 // The entry points share one argument gate (scrub_args_ok), the device calls
-// one window / tail launcher (run_windows_tail) and the CPU calls one column
-// loop (heal_stripe).
+// one window / tail launcher (run_windows_tail), the one-pass CRC calls one
+// body (scrub_crc_pass) and the CPU calls one column loop (heal_stripe).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -227,58 +227,6 @@ bool scrub_crc_one_pass(const hrs_codec* c, const uint8_t* const* rows, size_t s
   return true;
 }
 
-hrs_status run_scrub_crc(hrs_codec* c, const uint8_t* const* rows, size_t stride, size_t len, size_t nstripes,
-                         uint32_t* reports, size_t report_stride, const uint32_t* crc_in, uint32_t* crc_out,
-                         hipStream_t s, bool heal) {
-  const int n = c->n;
-  if (!scrub_crc_one_pass(c, rows, stride, len)) {
-    // two passes: the scrub or heal as it is, then the CRC of the n rows (the
-    // stream orders the heal's stores before the CRC pass reads them)
-    hrs_status st = run_scrub(c, rows, stride, len, nstripes, reports, report_stride, s, heal);
-    if (st != HRS_OK) return st;
-    const std::string kernel = c->last_kernel;
-    st = crc_scratch(c, crc_raw_bytes_for(len, nstripes, n), s);
-    if (st != HRS_OK) return st;
-    const std::vector<size_t> strides(n, stride);
-    st = crc_scratch_release(c, s, run_crc(c, rows, strides.data(), n, len, nstripes, crc_in, crc_out, s, c->crc_raw));
-    c->last_kernel = kernel;
-    return st;
-  }
-  hipError_t e = hrs::launch_scrub_init(reports, report_stride, n, nstripes, s);
-  if (e != hipSuccess) return hip_fail(c, e, "scrub init launch");
-  hrs_status st = crc_window_tables(c);
-  if (st != HRS_OK) return st;
-  hrs::ScrubCrcArgs a{};
-  for (int l = 0; l < n; ++l) a.rows[l] = rows[l];
-  a.stride = stride;
-  a.nwin = len / hrs::kWindowBytes;
-  a.ntasks = a.nwin * nstripes;
-  a.reports = reports;
-  a.report_stride = report_stride;
-  a.n = n;
-  a.p = c->p;
-  a.tables = c->crc_tables_a;
-  // scratch: the raw window CRCs, then (heal) the dirty-task count and list
-  const size_t raw_bytes = (a.ntasks * static_cast<size_t>(n) * 4 + 7) & ~static_cast<size_t>(7);
-  const size_t list_bytes = heal ? (1 + a.ntasks) * sizeof(uint64_t) : 0;
-  st = crc_scratch(c, raw_bytes + list_bytes, s);
-  if (st != HRS_OK) return st;
-  a.raw = c->crc_raw;
-  a.dirty = heal ? reinterpret_cast<uint64_t*>(reinterpret_cast<uint8_t*>(c->crc_raw) + raw_bytes) : nullptr;
-  const int cus = hrs::device_cu_count();
-  auto launches = [&]() -> hrs_status {
-    if (heal && (e = hipMemsetAsync(a.dirty, 0, sizeof(uint64_t), s)) != hipSuccess)
-      return hip_fail(c, e, "hipMemsetAsync");
-    if ((e = hrs::launch_scrub_crc(a, heal, cus, s)) != hipSuccess)
-      return hip_fail(c, e, heal ? "heal+crc launch" : "scrub+crc launch");
-    c->last_kernel = hrs::last_kernel();
-    if (heal && (e = hrs::launch_scrub_crc_redo(a, cus, s)) != hipSuccess) return hip_fail(c, e, "crc redo launch");
-    return crc_fold_windows(c, len, nstripes * static_cast<uint64_t>(n), crc_in, crc_out, s, c->crc_raw,
-                            hrs::kWindowBytes);
-  };
-  return crc_scratch_release(c, s, launches());
-}
-
 namespace {
 
 // hrs_scrub_dev and hrs_heal_dev.
@@ -403,65 +351,85 @@ hrs_status run_heal_erased(hrs_codec* c, uint8_t* const* rows, size_t stride, si
 // passes with overlapping ranges, so those keep the two passes.
 bool heal_erased_crc_fused_default(bool host_memory) { return host_memory; }
 
-hrs_status run_heal_erased_crc(hrs_codec* c, uint8_t* const* rows, size_t stride, size_t len, size_t nstripes,
-                               const std::vector<hrs::ErasePattern>& pats, const int32_t* pat, uint32_t* reports,
-                               size_t report_stride, const uint32_t* crc_in, uint32_t* crc_out, hipStream_t s,
-                               bool host_memory) {
+namespace {
+
+// The one-pass scrub, heal and heal with erasures with CRCs (hrs_scrub_crc.hip,
+// hrs_heal_erased_crc.hip), once its caller's route rule holds: empty reports,
+// the window tables and, with erasures (pats), their table through a batch
+// slot; then, under one lease of the raw-CRC scratch, the memset of the dirty
+// count (heal), `launch` (`what` names it in a launch error), the redo of the
+// dirty windows (heal) and the fold. heal: the rows are written.
+template <class Launch>
+hrs_status scrub_crc_pass(hrs_codec* c, const uint8_t* const* rows, size_t stride, size_t len, size_t nstripes,
+                          uint32_t* reports, size_t report_stride, const uint32_t* crc_in, uint32_t* crc_out,
+                          hipStream_t s, bool heal, const std::vector<hrs::ErasePattern>* pats, const int32_t* pat,
+                          const char* what, Launch launch) {
   const int n = c->n;
-  const bool fused = scrub_crc_one_pass(c, rows, stride, len) &&
-                     (c->kernel_mode == 3 || heal_erased_crc_fused_default(host_memory));
-  if (!fused) {
-    // two passes: the heal as it is, then the CRC of the n rows (the stream
-    // orders the heal's stores before the CRC pass reads them)
-    hrs_status st = run_heal_erased(c, rows, stride, len, nstripes, pats, pat, reports, report_stride, s);
-    if (st != HRS_OK) return st;
-    const std::string kernel = c->last_kernel;
-    st = crc_scratch(c, crc_raw_bytes_for(len, nstripes, n), s);
-    if (st != HRS_OK) return st;
-    const std::vector<size_t> strides(n, stride);
-    st = crc_scratch_release(c, s, run_crc(c, rows, strides.data(), n, len, nstripes, crc_in, crc_out, s, c->crc_raw));
-    c->last_kernel = kernel;
-    return st;
-  }
   hipError_t e = hrs::launch_scrub_init(reports, report_stride, n, nstripes, s);
   if (e != hipSuccess) return hip_fail(c, e, "scrub init launch");
   hrs_status st = crc_window_tables(c);
   if (st != HRS_OK) return st;
-  hrs::HealErasedCrcArgs a{};
-  for (int l = 0; l < n; ++l) a.c.rows[l] = rows[l];
-  a.c.stride = stride;
-  a.c.nwin = len / hrs::kWindowBytes;
-  a.c.ntasks = a.c.nwin * nstripes;
-  a.c.reports = reports;
-  a.c.report_stride = report_stride;
-  a.c.n = n;
-  a.c.p = c->p;
-  a.c.tables = c->crc_tables_a;
+  hrs::HealErasedCrcArgs h{};
+  hrs::ScrubCrcArgs& a = h.c;
+  for (int l = 0; l < n; ++l) a.rows[l] = rows[l];
+  a.stride = stride;
+  a.nwin = len / hrs::kWindowBytes;
+  a.ntasks = a.nwin * nstripes;
+  a.reports = reports;
+  a.report_stride = report_stride;
+  a.n = n;
+  a.p = c->p;
+  a.tables = c->crc_tables_a;
   hrs_codec::BatchSlot* sl = nullptr;
-  st = pattern_table(c, pats, pat, nstripes, s, &sl, &a.pats, &a.pat);
-  if (st != HRS_OK) return st;
-  // scratch: the raw window CRCs, then the dirty-task count and list
-  const size_t raw_bytes = (a.c.ntasks * static_cast<size_t>(n) * 4 + 7) & ~static_cast<size_t>(7);
-  const size_t list_bytes = (1 + a.c.ntasks) * sizeof(uint64_t);
-  st = crc_scratch(c, raw_bytes + list_bytes, s);
-  if (st != HRS_OK) {
-    slot_used(sl, s);
-    return st;
-  }
-  a.c.raw = c->crc_raw;
-  a.c.dirty = reinterpret_cast<uint64_t*>(reinterpret_cast<uint8_t*>(c->crc_raw) + raw_bytes);
+  if (pats && (st = pattern_table(c, *pats, pat, nstripes, s, &sl, &h.pats, &h.pat)) != HRS_OK) return st;
+  // scratch: the raw window CRCs, then (heal) the dirty-task count and list
+  const size_t raw_bytes = (a.ntasks * static_cast<size_t>(n) * 4 + 7) & ~static_cast<size_t>(7);
+  const size_t list_bytes = heal ? (1 + a.ntasks) * sizeof(uint64_t) : 0;
   const int cus = hrs::device_cu_count();
-  auto launches = [&]() -> hrs_status {
-    if ((e = hipMemsetAsync(a.c.dirty, 0, sizeof(uint64_t), s)) != hipSuccess) return hip_fail(c, e, "hipMemsetAsync");
-    if ((e = hrs::launch_heal_erased_crc(a, cus, s)) != hipSuccess) return hip_fail(c, e, "heal erased+crc launch");
+  st = with_crc_scratch(c, raw_bytes + list_bytes, s, [&]() -> hrs_status {
+    a.raw = c->crc_raw;
+    a.dirty = heal ? reinterpret_cast<uint64_t*>(reinterpret_cast<uint8_t*>(c->crc_raw) + raw_bytes) : nullptr;
+    if (heal && (e = hipMemsetAsync(a.dirty, 0, sizeof(uint64_t), s)) != hipSuccess)
+      return hip_fail(c, e, "hipMemsetAsync");
+    if ((e = launch(h, cus)) != hipSuccess) return hip_fail(c, e, what);
     c->last_kernel = hrs::last_kernel();
-    if ((e = hrs::launch_scrub_crc_redo(a.c, cus, s)) != hipSuccess) return hip_fail(c, e, "crc redo launch");
-    return crc_fold_windows(c, len, nstripes * static_cast<uint64_t>(n), crc_in, crc_out, s, c->crc_raw,
-                            hrs::kWindowBytes);
-  };
-  st = crc_scratch_release(c, s, launches());
-  slot_used(sl, s);
+    if (heal && (e = hrs::launch_scrub_crc_redo(a, cus, s)) != hipSuccess) return hip_fail(c, e, "crc redo launch");
+    return crc_fold(c, len, nstripes * static_cast<uint64_t>(n), crc_in, crc_out, s, c->crc_raw, hrs::kWindowBytes);
+  });
+  if (sl) slot_used(sl, s);  // on every exit: the table may be in use whether or not every launch went out
   return st;
+}
+
+}  // namespace
+
+hrs_status run_scrub_crc(hrs_codec* c, const uint8_t* const* rows, size_t stride, size_t len, size_t nstripes,
+                         uint32_t* reports, size_t report_stride, const uint32_t* crc_in, uint32_t* crc_out,
+                         hipStream_t s, bool heal) {
+  if (!scrub_crc_one_pass(c, rows, stride, len)) {
+    // two passes: the scrub or heal as it is, then the CRC of the n rows (the
+    // stream orders the heal's stores before the CRC pass reads them)
+    const hrs_status st = run_scrub(c, rows, stride, len, nstripes, reports, report_stride, s, heal);
+    return st != HRS_OK ? st : crc_rows(c, rows, c->n, stride, len, nstripes, crc_in, crc_out, s);
+  }
+  auto launch = [&](const hrs::HealErasedCrcArgs& h, int cus) { return hrs::launch_scrub_crc(h.c, heal, cus, s); };
+  return scrub_crc_pass(c, rows, stride, len, nstripes, reports, report_stride, crc_in, crc_out, s, heal, nullptr,
+                        nullptr, heal ? "heal+crc launch" : "scrub+crc launch", launch);
+}
+
+hrs_status run_heal_erased_crc(hrs_codec* c, uint8_t* const* rows, size_t stride, size_t len, size_t nstripes,
+                               const std::vector<hrs::ErasePattern>& pats, const int32_t* pat, uint32_t* reports,
+                               size_t report_stride, const uint32_t* crc_in, uint32_t* crc_out, hipStream_t s,
+                               bool host_memory) {
+  const bool fused = scrub_crc_one_pass(c, rows, stride, len) &&
+                     (c->kernel_mode == 3 || heal_erased_crc_fused_default(host_memory));
+  if (!fused) {
+    // two passes: the heal as it is, then the CRC of the n rows (as above)
+    const hrs_status st = run_heal_erased(c, rows, stride, len, nstripes, pats, pat, reports, report_stride, s);
+    return st != HRS_OK ? st : crc_rows(c, rows, c->n, stride, len, nstripes, crc_in, crc_out, s);
+  }
+  auto launch = [&](const hrs::HealErasedCrcArgs& h, int cus) { return hrs::launch_heal_erased_crc(h, cus, s); };
+  return scrub_crc_pass(c, rows, stride, len, nstripes, reports, report_stride, crc_in, crc_out, s, true, &pats, pat,
+                        "heal erased+crc launch", launch);
 }
 
 namespace {

@@ -1,6 +1,7 @@
 """CPU tests of the argument rules of the six device entry points of
-hrs_dispatch.cpp (hrs_encode_dev, hrs_decode_dev, hrs_apply_dev, hrs_crc32_dev,
-hrs_encode_crc_dev, hrs_decode_crc_dev) on a host-only handle: every rule that
+hrs_dispatch.cpp (hrs_encode_dev, hrs_decode_dev, hrs_apply_dev) and
+hrs_crc_api.cpp (hrs_crc32_dev, hrs_encode_crc_dev, hrs_decode_crc_dev) on a
+host-only handle: every rule that
 is settled before a device is selected, in the order each entry applies them
 (handle, argument block, NULL rows, empty call, erased / not-to-read
 locations, device). The pointers stand for device memory and are never read:

@@ -10,8 +10,9 @@ hrs_crc32_dev): every byte a call could touch lives in a guarded arena
   output rows the call must not write still poisoned;
 - hrs_last_kernel names the kernel the case is meant to exercise. The names
   in the tables are literals read off the dispatch source (run_apply in
-  hrs_dispatch.cpp, launch_batch in hrs_batch_api.cpp, the launch_* functions
-  of the .hip files), not computed by a second planner.
+  hrs_dispatch.cpp, the CRC routes in hrs_crc_api.cpp, launch_batch in
+  hrs_batch_api.cpp, the launch_* functions of the .hip files), not computed
+  by a second planner.
 
 Placements: "aligned" and "gap16" (16 spare bytes per stripe) keep rows and
 strides on 16-byte boundaries, so the vector kernels run; "shift" (rows start
