@@ -8,12 +8,18 @@ hops location order — rows [0, p) parity, [p, p+k) data — i.e. exactly the
 Decode outputs go to a separate `out[S, e, L]` tensor.
 
 All calls are asynchronous on the current torch stream of the tensors' device.
+
+Every argument rule is stated once, in the helpers of the first section; a
+family of library calls that share a signature has one private body, which
+takes `crcs`: None for the call without CRCs, else its (crc_in[, crc_out]).
 """
 import numpy as np
 
 from . import _lib
 from ._lib import int_array, ptr_array
 
+
+# ---- device arguments
 
 def _rows(views):
     """[S, L] row views -> (pointer array, stride bytes, L, S)."""
@@ -38,15 +44,20 @@ def _rows(views):
     return ptrs, stride, L, S
 
 
-def _stripe_rows(t, locs):
+def _stripe_rows(t, locs, n=None):
     """Rows `locs` (None = not passed) of a [S, m, L] uint8 device tensor ->
     (pointer array, stride bytes, L, S), the same as _rows over the views
     t[:, loc, :] but computed from t's own pointer and strides: building m
-    tensor views costs ~3 us each in Python, more than a small launch."""
+    tensor views costs ~3 us each in Python, more than a small launch. With n,
+    t is a batch of a code with n locations and must be [S, n, L]."""
     torch = _lib.torch
     if t.dtype != torch.uint8 or t.dim() != 3 or t.stride(2) != 1 or not t.is_cuda:
         raise ValueError("stripes must be a [S, m, L] uint8 device tensor with unit byte stride")
     S, m, L = t.shape
+    if n is not None and m != n:
+        raise ValueError(f"stripes must be [S, {n}, L]")
+    if locs is None:  # decode_batch: the library takes t's own pointer and both strides
+        return None, None, L, S
     base, s_stripe, s_row = t.data_ptr(), t.stride(0), t.stride(1)
     for loc in locs:
         if loc is not None and not 0 <= loc < m:
@@ -55,147 +66,57 @@ def _stripe_rows(t, locs):
     return ptrs, (s_stripe if S > 1 else L), L, S
 
 
+def _code_stripes(code, stripes):
+    """A device batch stripes[S, n, L] of this code -> (pointer array of its n
+    rows, stride bytes, L, S, stripes): _stripe_rows' tuple and the tensor
+    whose device and stream the call uses."""
+    n = code.stripeSize() + code.paritySize()
+    return (*_stripe_rows(stripes, range(n), n), stripes)
+
+
+def _code_rows(code, row_views):
+    """The same batch as n explicit [S, L] row views, one per location in hops
+    order -> _code_stripes' tuple, the first view standing for the tensor."""
+    n = code.stripeSize() + code.paritySize()
+    if len(row_views) != n or any(v is None for v in row_views):
+        raise ValueError(f"need {n} row views")
+    return (*_rows(row_views), row_views[0])
+
+
 def _stream(t):
     return _lib.torch.cuda.current_stream(t.device).cuda_stream
 
 
-def encode_stripes(code, stripes):
-    """Parity rows of every stripe from its data rows (encodeBulk over S stripes)."""
-    k, p = code.stripeSize(), code.paritySize()
-    if stripes.dim() != 3 or stripes.shape[1] != k + p:
-        raise ValueError(f"stripes must be [S, {k + p}, L]")
-    ins, s_in, L, S = _stripe_rows(stripes, range(p, p + k))
-    outs, s_out, _, _ = _stripe_rows(stripes, range(p))
-    code._check(_lib.lib().hrs_encode_dev(code._handle(), ins, s_in, outs, s_out, L, S, _stream(stripes)))
+# A device batch without bytes (L == 0 or S == 0) is answered here, not by the
+# library: torch gives a tensor without elements a null data_ptr(), which the
+# scrub, heal and decode entry points refuse as a NULL row. Such a call has
+# nothing to do, so the bodies below skip it (`if L and S`); _dev_crcs has
+# filled its CRCs and _dev_reports its reports.
 
 
-def encode_stripes_crc(code, stripes, crc_in=None):
-    """Encode every stripe and return the CRC-32 (java.util.zip.CRC32) of its
-    cells in one pass, as Encoder.encodeStripe keeps them with
-    computeBlockChecksum (Encoder.java:408-450): an int32 tensor [S, k + p],
-    columns [source 0..k-1, parity 0..p-1] holding the uint32 CRC bits.
-    crc_in ([S, k + p] int32, same layout) continues running CRCs across
-    successive cells (CRC32.update chaining)."""
+def _dev_crcs(shape, ref, L, S, crc_in, crc_out=None):
+    """(crc_in pointer or None, the int32 result tensor) of a device call over
+    S stripes of L-byte cells on ref's device; _host_crcs' counterpart."""
     torch = _lib.torch
-    k, p = code.stripeSize(), code.paritySize()
-    if stripes.dim() != 3 or stripes.shape[1] != k + p:
-        raise ValueError(f"stripes must be [S, {k + p}, L]")
-    ins, s_in, L, S = _stripe_rows(stripes, range(p, p + k))
-    outs, s_out, _, _ = _stripe_rows(stripes, range(p))
-    crc = torch.empty((S, k + p), dtype=torch.int32, device=stripes.device)
-    cin = None
-    if crc_in is not None:
-        if crc_in.shape != crc.shape or crc_in.dtype != torch.int32 or not crc_in.is_contiguous():
-            raise ValueError(f"crc_in must be a contiguous int32 tensor [S, {k + p}]")
-        cin = crc_in.data_ptr()
-    code._check(_lib.lib().hrs_encode_crc_dev(code._handle(), ins, s_in, outs, s_out, L, S, cin, crc.data_ptr(),
-                                              _stream(stripes)))
-    return crc
-
-
-def encode_rows(code, data_rows, parity_rows):
-    """encodeBulk with explicit [S, L] row views (k data, p parity)."""
-    ins, s_in, L, S = _rows(data_rows)
-    outs, s_out, L2, S2 = _rows(parity_rows)
-    if (L, S) != (L2, S2):
-        raise ValueError("data and parity views differ in shape")
-    code._check(_lib.lib().hrs_encode_dev(code._handle(), ins, s_in, outs, s_out, L, S, _stream(data_rows[0])))
-
-
-def decode_stripes(code, stripes, erased, not_to_read, out):
-    """decodeBulk 5-arg over S stripes: out[S, e, L] <- the erased locations.
-    Rows of `stripes` at not_to_read locations are never read."""
-    n = code.stripeSize() + code.paritySize()
-    if stripes.dim() != 3 or stripes.shape[1] != n:
-        raise ValueError(f"stripes must be [S, {n}, L]")
-    ntr = set(not_to_read)
-    rows, s_in, L, S = _stripe_rows(stripes, [None if loc in ntr else loc for loc in range(n)])
-    outs, s_out, L2, S2 = _stripe_rows(out, range(len(erased)))
-    if (L, S) != (L2, S2):
-        raise ValueError("out must be [S, e, L]")
-    code._check(_lib.lib().hrs_decode_dev(
-        code._handle(), rows, s_in, outs, s_out, int_array(erased), len(erased),
-        int_array(not_to_read), len(not_to_read), L, S, _stream(stripes)))
-
-
-def decode_stripes_crc(code, stripes, erased, not_to_read, out, crc_in=None):
-    """decode_stripes plus the CRC-32 (java.util.zip.CRC32) of every repaired
-    cell in one pass, as the Decoder checks a repaired block against the
-    NameNode's checksum (Decoder.java:222-229, :645-655): returns an int32
-    tensor [S, e] of the uint32 CRC bits; crc_in (same layout) continues
-    running CRCs across successive cells."""
-    torch = _lib.torch
-    n = code.stripeSize() + code.paritySize()
-    if stripes.dim() != 3 or stripes.shape[1] != n:
-        raise ValueError(f"stripes must be [S, {n}, L]")
-    ntr = set(not_to_read)
-    rows, s_in, L, S = _stripe_rows(stripes, [None if loc in ntr else loc for loc in range(n)])
-    outs, s_out, L2, S2 = _stripe_rows(out, range(len(erased)))
-    if (L, S) != (L2, S2):
-        raise ValueError("out must be [S, e, L]")
-    crc = torch.empty((S, len(erased)), dtype=torch.int32, device=stripes.device)
-    cin = None
-    if crc_in is not None:
-        if crc_in.shape != crc.shape or crc_in.dtype != torch.int32 or not crc_in.is_contiguous():
-            raise ValueError(f"crc_in must be a contiguous int32 tensor [S, {len(erased)}]")
-        cin = crc_in.data_ptr()
-    code._check(_lib.lib().hrs_decode_crc_dev(
-        code._handle(), rows, s_in, outs, s_out, int_array(erased), len(erased),
-        int_array(not_to_read), len(not_to_read), L, S, cin, crc.data_ptr(), _stream(stripes)))
-    return crc
-
-
-def decode_batch(code, stripes, erased, out):
-    """Repair every stripe of stripes[S, n, L] from its own erasure list, in one
-    launch (hrs_decode_batch_dev): erased is an int array [S, E] of hops
-    locations (ascending per stripe, -1 padded; a row of -1 = nothing lost);
-    out[S, E, L] receives stripe s's repaired rows in that order. Survivors are
-    the ones locationsToReadForDecode picks, as Decoder.fixErasedBlockImpl does."""
-    n = code.stripeSize() + code.paritySize()
-    if stripes.dim() != 3 or stripes.shape[1] != n or stripes.stride(2) != 1:
-        raise ValueError(f"stripes must be [S, {n}, L] with unit byte stride")
-    e = np.ascontiguousarray(np.asarray(erased, dtype=np.int32))
-    S, L = stripes.shape[0], stripes.shape[2]
-    if e.ndim != 2 or e.shape[0] != S:
-        raise ValueError("erased must be [S, E]")
-    if out.dim() != 3 or tuple(out.shape) != (S, e.shape[1], L) or out.stride(2) != 1 or out.device != stripes.device:
-        raise ValueError("out must be [S, E, L] on the stripes' device")
-    code._check(_lib.lib().hrs_decode_batch_dev(
-        code._handle(), stripes.data_ptr(), stripes.stride(1), stripes.stride(0), e.ctypes.data, e.shape[1],
-        out.data_ptr(), out.stride(1), out.stride(0), L, S, _stream(stripes)))
-
-
-def decode_batch_crc(code, stripes, erased, out, crc_in=None, crc_out=None):
-    """decode_batch plus the CRC-32 (java.util.zip.CRC32) of every repaired cell
-    in one pass (hrs_decode_batch_crc_dev): returns an int32 tensor [S, E] of
-    the uint32 CRC bits, entry [s, t] for output t of stripe s. crc_in (same
-    layout) continues running CRCs across successive cells; an entry past its
-    stripe's losses continues over no bytes and keeps its crc_in value (0
-    without crc_in). crc_out: the tensor to fill and return (it may be crc_in
-    itself) instead of a new one."""
-    torch = _lib.torch
-    n = code.stripeSize() + code.paritySize()
-    if stripes.dim() != 3 or stripes.shape[1] != n or stripes.stride(2) != 1:
-        raise ValueError(f"stripes must be [S, {n}, L] with unit byte stride")
-    e = np.ascontiguousarray(np.asarray(erased, dtype=np.int32))
-    S, L = stripes.shape[0], stripes.shape[2]
-    if e.ndim != 2 or e.shape[0] != S:
-        raise ValueError("erased must be [S, E]")
-    if out.dim() != 3 or tuple(out.shape) != (S, e.shape[1], L) or out.stride(2) != 1 or out.device != stripes.device:
-        raise ValueError("out must be [S, E, L] on the stripes' device")
     for name, t in (("crc_in", crc_in), ("crc_out", crc_out)):
-        if t is not None and (tuple(t.shape) != (S, e.shape[1]) or t.dtype != torch.int32 or not t.is_contiguous()
-                              or t.device != stripes.device):
-            raise ValueError(f"{name} must be a contiguous int32 tensor [S, {e.shape[1]}] on the stripes' device")
-    crc = crc_out if crc_out is not None else torch.empty((S, e.shape[1]), dtype=torch.int32, device=stripes.device)
-    if L == 0 and crc is not crc_in:  # the call touches nothing: every CRC continues over no bytes
+        if t is not None and (not isinstance(t, torch.Tensor) or tuple(t.shape) != shape or t.dtype != torch.int32
+                              or not t.is_contiguous() or t.device != ref.device):
+            raise ValueError(f"{name} must be a contiguous int32 tensor [S, {shape[1]}] on the stripes' device")
+    crc = crc_out if crc_out is not None else torch.empty(shape, dtype=torch.int32, device=ref.device)
+    if (L == 0 or S == 0) and crc is not crc_in:  # the call touches nothing: every CRC continues over no bytes
         crc.zero_() if crc_in is None else crc.copy_(crc_in)
-    code._check(_lib.lib().hrs_decode_batch_crc_dev(
-        code._handle(), stripes.data_ptr(), stripes.stride(1), stripes.stride(0), e.ctypes.data, e.shape[1],
-        out.data_ptr(), out.stride(1), out.stride(0), L, S, None if crc_in is None else crc_in.data_ptr(),
-        crc.data_ptr(), _stream(stripes)))
-    return crc
+    return (None if crc_in is None else crc_in.data_ptr()), crc
 
+
+def _decode_erased(erased, S):
+    """The decode family's erasure lists as a contiguous host int32 [S, E] array."""
+    e = np.ascontiguousarray(np.asarray(erased, dtype=np.int32))
+    if e.ndim != 2 or e.shape[0] != S:
+        raise ValueError("erased must be [S, E]")
+    return e
+
+
+# ---- host arguments
 
 def _host_crcs(shape, L, crc_in, crc_out):
     """(crc_in pointer or None, the uint32 result array) of a host batch of L-byte cells."""
@@ -224,75 +145,22 @@ def _host_ptr(a, name, writable=False):
     return a.ctypes.data, a.shape, tuple(x // a.itemsize for x in a.strides)
 
 
-def decode_batch_host(code, stripes, erased, out):
-    """hrs_decode_batch_host: decode_batch for stripes[S, n, L] and out[S, E, L]
-    in HOST memory (numpy arrays or CPU tensors; pinned ones are DMA'd
-    directly). Only each stripe's survivors go over PCIe, only the repaired
-    cells come back; chunks of stripes pipeline through the device."""
+def _host_batch(code, stripes, writable=False):
+    """A host batch stripes[S, n, L] of this code -> (pointer, row stride,
+    stripe stride, L, S), the order the library's host-batch calls take them in."""
     n = code.stripeSize() + code.paritySize()
-    sp, sshape, sstr = _host_ptr(stripes, "stripes")
+    sp, sshape, sstr = _host_ptr(stripes, "stripes", writable)
+    if len(sshape) != 3 or sshape[1] != n or sstr[2] != 1:
+        raise ValueError(f"stripes must be [S, {n}, L] with unit byte stride")
+    return sp, sstr[1], sstr[0], sshape[2], sshape[0]
+
+
+def _host_out(out, S, E, L):
+    """The decode family's host out[S, E, L] -> (pointer, row stride, stripe stride)."""
     op, oshape, ostr = _host_ptr(out, "out", writable=True)
-    e = np.ascontiguousarray(np.asarray(erased, dtype=np.int32))
-    if len(sshape) != 3 or sshape[1] != n or sstr[2] != 1:
-        raise ValueError(f"stripes must be [S, {n}, L] with unit byte stride")
-    S, L = sshape[0], sshape[2]
-    if e.ndim != 2 or e.shape[0] != S:
-        raise ValueError("erased must be [S, E]")
-    if len(oshape) != 3 or tuple(oshape) != (S, e.shape[1], L) or ostr[2] != 1:
+    if len(oshape) != 3 or tuple(oshape) != (S, E, L) or ostr[2] != 1:
         raise ValueError("out must be [S, E, L]")
-    code._check(_lib.lib().hrs_decode_batch_host(
-        code._handle(), sp, sstr[1], sstr[0], e.ctypes.data, e.shape[1], op, ostr[1], ostr[0], L, S))
-
-
-def encode_batch_host(code, stripes):
-    """hrs_encode_batch_host: parity rows of every stripe of a HOST batch
-    stripes[S, n, L] (hops order) from its data rows, in place."""
-    n = code.stripeSize() + code.paritySize()
-    sp, sshape, sstr = _host_ptr(stripes, "stripes", writable=True)
-    if len(sshape) != 3 or sshape[1] != n or sstr[2] != 1:
-        raise ValueError(f"stripes must be [S, {n}, L] with unit byte stride")
-    code._check(_lib.lib().hrs_encode_batch_host(code._handle(), sp, sstr[1], sstr[0], sshape[2], sshape[0]))
-
-
-def decode_batch_host_crc(code, stripes, erased, out, crc_in=None, crc_out=None):
-    """hrs_decode_batch_host_crc: decode_batch_host plus the CRC-32 of every
-    repaired cell, computed on the GPU in the same pass: returns a numpy uint32
-    array [S, E] (entry [s, t] for output t of stripe s; entries past a
-    stripe's losses keep their crc_in value, 0 without crc_in). crc_in (uint32
-    [S, E]) continues running CRCs; crc_out: the array to fill and return (it
-    may be crc_in itself) instead of a new one."""
-    n = code.stripeSize() + code.paritySize()
-    sp, sshape, sstr = _host_ptr(stripes, "stripes")
-    op, oshape, ostr = _host_ptr(out, "out", writable=True)
-    e = np.ascontiguousarray(np.asarray(erased, dtype=np.int32))
-    if len(sshape) != 3 or sshape[1] != n or sstr[2] != 1:
-        raise ValueError(f"stripes must be [S, {n}, L] with unit byte stride")
-    S, L = sshape[0], sshape[2]
-    if e.ndim != 2 or e.shape[0] != S:
-        raise ValueError("erased must be [S, E]")
-    if len(oshape) != 3 or tuple(oshape) != (S, e.shape[1], L) or ostr[2] != 1:
-        raise ValueError("out must be [S, E, L]")
-    cin, crc = _host_crcs((S, e.shape[1]), L, crc_in, crc_out)
-    code._check(_lib.lib().hrs_decode_batch_host_crc(
-        code._handle(), sp, sstr[1], sstr[0], e.ctypes.data, e.shape[1], op, ostr[1], ostr[0], L, S, cin,
-        crc.ctypes.data))
-    return crc
-
-
-def encode_batch_host_crc(code, stripes, crc_in=None, crc_out=None):
-    """hrs_encode_batch_host_crc: encode_batch_host plus the CRC-32 of every
-    cell, as Encoder.encodeStripe keeps them with computeBlockChecksum: returns
-    a numpy uint32 array [S, k + p], columns [source 0..k-1, parity 0..p-1]
-    (encode_stripes_crc's order). crc_in (same layout) continues running CRCs;
-    crc_out: the array to fill and return (it may be crc_in itself)."""
-    n = code.stripeSize() + code.paritySize()
-    sp, sshape, sstr = _host_ptr(stripes, "stripes", writable=True)
-    if len(sshape) != 3 or sshape[1] != n or sstr[2] != 1:
-        raise ValueError(f"stripes must be [S, {n}, L] with unit byte stride")
-    cin, crc = _host_crcs((sshape[0], n), sshape[2], crc_in, crc_out)
-    code._check(_lib.lib().hrs_encode_batch_host_crc(code._handle(), sp, sstr[1], sstr[0], sshape[2], sshape[0], cin,
-                                                     crc.ctypes.data))
-    return crc
+    return op, ostr[1], ostr[0]
 
 
 def _codec_array(codes):
@@ -302,38 +170,195 @@ def _codec_array(codes):
     return codes, ptr_array([c._handle().value for c in codes])
 
 
+# ---- encode and decode on the device
+
+def _encode_stripes(code, stripes, crcs=None):
+    k, p = code.stripeSize(), code.paritySize()
+    ins, s_in, L, S = _stripe_rows(stripes, range(p, p + k), k + p)
+    outs, s_out, _, _ = _stripe_rows(stripes, range(p))
+    args = (code._handle(), ins, s_in, outs, s_out, L, S)
+    if crcs is None:
+        code._check(_lib.lib().hrs_encode_dev(*args, _stream(stripes)))
+        return None
+    cin, crc = _dev_crcs((S, k + p), stripes, L, S, *crcs)
+    code._check(_lib.lib().hrs_encode_crc_dev(*args, cin, crc.data_ptr(), _stream(stripes)))
+    return crc
+
+
+def encode_stripes(code, stripes):
+    """Parity rows of every stripe from its data rows (encodeBulk over S stripes)."""
+    _encode_stripes(code, stripes)
+
+
+def encode_stripes_crc(code, stripes, crc_in=None):
+    """Encode every stripe and return the CRC-32 (java.util.zip.CRC32) of its
+    cells in one pass, as Encoder.encodeStripe keeps them with
+    computeBlockChecksum (Encoder.java:408-450): an int32 tensor [S, k + p],
+    columns [source 0..k-1, parity 0..p-1] holding the uint32 CRC bits.
+    crc_in ([S, k + p] int32, same layout) continues running CRCs across
+    successive cells (CRC32.update chaining)."""
+    return _encode_stripes(code, stripes, (crc_in,))
+
+
+def encode_rows(code, data_rows, parity_rows):
+    """encodeBulk with explicit [S, L] row views (k data, p parity)."""
+    ins, s_in, L, S = _rows(data_rows)
+    outs, s_out, L2, S2 = _rows(parity_rows)
+    if (L, S) != (L2, S2):
+        raise ValueError("data and parity views differ in shape")
+    code._check(_lib.lib().hrs_encode_dev(code._handle(), ins, s_in, outs, s_out, L, S, _stream(data_rows[0])))
+
+
+def _decode_stripes(code, stripes, erased, not_to_read, out, crcs=None):
+    n = code.stripeSize() + code.paritySize()
+    ntr = set(not_to_read)
+    rows, s_in, L, S = _stripe_rows(stripes, [None if loc in ntr else loc for loc in range(n)], n)
+    outs, s_out, L2, S2 = _stripe_rows(out, range(len(erased)))
+    if (L, S) != (L2, S2):
+        raise ValueError("out must be [S, e, L]")
+    args = (code._handle(), rows, s_in, outs, s_out, int_array(erased), len(erased), int_array(not_to_read),
+            len(not_to_read), L, S)
+    if crcs is None:
+        if L and S:
+            code._check(_lib.lib().hrs_decode_dev(*args, _stream(stripes)))
+        return None
+    cin, crc = _dev_crcs((S, len(erased)), stripes, L, S, *crcs)
+    if L and S:
+        code._check(_lib.lib().hrs_decode_crc_dev(*args, cin, crc.data_ptr(), _stream(stripes)))
+    return crc
+
+
+def decode_stripes(code, stripes, erased, not_to_read, out):
+    """decodeBulk 5-arg over S stripes: out[S, e, L] <- the erased locations.
+    Rows of `stripes` at not_to_read locations are never read."""
+    _decode_stripes(code, stripes, erased, not_to_read, out)
+
+
+def decode_stripes_crc(code, stripes, erased, not_to_read, out, crc_in=None):
+    """decode_stripes plus the CRC-32 (java.util.zip.CRC32) of every repaired
+    cell in one pass, as the Decoder checks a repaired block against the
+    NameNode's checksum (Decoder.java:222-229, :645-655): returns an int32
+    tensor [S, e] of the uint32 CRC bits; crc_in (same layout) continues
+    running CRCs across successive cells."""
+    return _decode_stripes(code, stripes, erased, not_to_read, out, (crc_in,))
+
+
+def _decode_batch(code, stripes, erased, out, crcs=None):
+    _, _, L, S = _stripe_rows(stripes, None, code.stripeSize() + code.paritySize())
+    e = _decode_erased(erased, S)
+    if (out.dim() != 3 or tuple(out.shape) != (S, e.shape[1], L) or out.stride(2) != 1
+            or out.dtype != _lib.torch.uint8 or out.device != stripes.device):
+        raise ValueError("out must be [S, E, L] on the stripes' device")
+    args = (code._handle(), stripes.data_ptr(), stripes.stride(1), stripes.stride(0), e.ctypes.data, e.shape[1],
+            out.data_ptr(), out.stride(1), out.stride(0), L, S)
+    if crcs is None:
+        if L and S:
+            code._check(_lib.lib().hrs_decode_batch_dev(*args, _stream(stripes)))
+        return None
+    cin, crc = _dev_crcs((S, e.shape[1]), stripes, L, S, *crcs)
+    if L and S:
+        code._check(_lib.lib().hrs_decode_batch_crc_dev(*args, cin, crc.data_ptr(), _stream(stripes)))
+    return crc
+
+
+def decode_batch(code, stripes, erased, out):
+    """Repair every stripe of stripes[S, n, L] from its own erasure list, in one
+    launch (hrs_decode_batch_dev): erased is an int array [S, E] of hops
+    locations (ascending per stripe, -1 padded; a row of -1 = nothing lost);
+    out[S, E, L] receives stripe s's repaired rows in that order. Survivors are
+    the ones locationsToReadForDecode picks, as Decoder.fixErasedBlockImpl does."""
+    _decode_batch(code, stripes, erased, out)
+
+
+def decode_batch_crc(code, stripes, erased, out, crc_in=None, crc_out=None):
+    """decode_batch plus the CRC-32 (java.util.zip.CRC32) of every repaired cell
+    in one pass (hrs_decode_batch_crc_dev): returns an int32 tensor [S, E] of
+    the uint32 CRC bits, entry [s, t] for output t of stripe s. crc_in (same
+    layout) continues running CRCs across successive cells; an entry past its
+    stripe's losses continues over no bytes and keeps its crc_in value (0
+    without crc_in). crc_out: the tensor to fill and return (it may be crc_in
+    itself) instead of a new one."""
+    return _decode_batch(code, stripes, erased, out, (crc_in, crc_out))
+
+
+# ---- encode and decode over host batches
+
+def _decode_batch_host(code, head, call, stripes, erased, out, crcs=None):
+    """The library's `call` over a host batch; `head` is its leading handle
+    argument, or a device set's handle array and count with `code` its first
+    codec."""
+    sp, row_stride, stripe_stride, L, S = _host_batch(code, stripes)
+    e = _decode_erased(erased, S)
+    args = (*head, sp, row_stride, stripe_stride, e.ctypes.data, e.shape[1], *_host_out(out, S, e.shape[1], L), L, S)
+    if crcs is None:
+        code._check(call(*args))
+        return None
+    cin, crc = _host_crcs((S, e.shape[1]), L, *crcs)
+    code._check(call(*args, cin, crc.ctypes.data))
+    return crc
+
+
+def _encode_batch_host(code, head, call, stripes, crcs=None):
+    """As _decode_batch_host; the stripes are written in place."""
+    sp, row_stride, stripe_stride, L, S = _host_batch(code, stripes, writable=True)
+    args = (*head, sp, row_stride, stripe_stride, L, S)
+    if crcs is None:
+        code._check(call(*args))
+        return None
+    cin, crc = _host_crcs((S, code.stripeSize() + code.paritySize()), L, *crcs)
+    code._check(call(*args, cin, crc.ctypes.data))
+    return crc
+
+
+def decode_batch_host(code, stripes, erased, out):
+    """hrs_decode_batch_host: decode_batch for stripes[S, n, L] and out[S, E, L]
+    in HOST memory (numpy arrays or CPU tensors; pinned ones are DMA'd
+    directly). Only each stripe's survivors go over PCIe, only the repaired
+    cells come back; chunks of stripes pipeline through the device."""
+    _decode_batch_host(code, (code._handle(),), _lib.lib().hrs_decode_batch_host, stripes, erased, out)
+
+
+def encode_batch_host(code, stripes):
+    """hrs_encode_batch_host: parity rows of every stripe of a HOST batch
+    stripes[S, n, L] (hops order) from its data rows, in place."""
+    _encode_batch_host(code, (code._handle(),), _lib.lib().hrs_encode_batch_host, stripes)
+
+
+def decode_batch_host_crc(code, stripes, erased, out, crc_in=None, crc_out=None):
+    """hrs_decode_batch_host_crc: decode_batch_host plus the CRC-32 of every
+    repaired cell, computed on the GPU in the same pass: returns a numpy uint32
+    array [S, E] (entry [s, t] for output t of stripe s; entries past a
+    stripe's losses keep their crc_in value, 0 without crc_in). crc_in (uint32
+    [S, E]) continues running CRCs; crc_out: the array to fill and return (it
+    may be crc_in itself) instead of a new one."""
+    return _decode_batch_host(code, (code._handle(),), _lib.lib().hrs_decode_batch_host_crc, stripes, erased, out,
+                              (crc_in, crc_out))
+
+
+def encode_batch_host_crc(code, stripes, crc_in=None, crc_out=None):
+    """hrs_encode_batch_host_crc: encode_batch_host plus the CRC-32 of every
+    cell, as Encoder.encodeStripe keeps them with computeBlockChecksum: returns
+    a numpy uint32 array [S, k + p], columns [source 0..k-1, parity 0..p-1]
+    (encode_stripes_crc's order). crc_in (same layout) continues running CRCs;
+    crc_out: the array to fill and return (it may be crc_in itself)."""
+    return _encode_batch_host(code, (code._handle(),), _lib.lib().hrs_encode_batch_host_crc, stripes,
+                              (crc_in, crc_out))
+
+
 def decode_batch_host_multi(codes, stripes, erased, out):
     """hrs_decode_batch_host_multi: decode_batch_host over a device set. `codes`
     are distinct codecs of one code, each on the device it should use; the
     stripes split into len(codes) contiguous ranges, one per codec, run on
     their own host threads (one host link per device)."""
     codes, arr = _codec_array(codes)
-    n = codes[0].stripeSize() + codes[0].paritySize()
-    sp, sshape, sstr = _host_ptr(stripes, "stripes")
-    op, oshape, ostr = _host_ptr(out, "out", writable=True)
-    e = np.ascontiguousarray(np.asarray(erased, dtype=np.int32))
-    if len(sshape) != 3 or sshape[1] != n or sstr[2] != 1:
-        raise ValueError(f"stripes must be [S, {n}, L] with unit byte stride")
-    S, L = sshape[0], sshape[2]
-    if e.ndim != 2 or e.shape[0] != S:
-        raise ValueError("erased must be [S, E]")
-    if len(oshape) != 3 or tuple(oshape) != (S, e.shape[1], L) or ostr[2] != 1:
-        raise ValueError("out must be [S, E, L]")
-    _lib.check(_lib.lib().hrs_decode_batch_host_multi(
-        arr, len(codes), sp, sstr[1], sstr[0], e.ctypes.data, e.shape[1], op, ostr[1], ostr[0], L, S),
-        codes[0]._h)
+    _decode_batch_host(codes[0], (arr, len(codes)), _lib.lib().hrs_decode_batch_host_multi, stripes, erased, out)
 
 
 def encode_batch_host_multi(codes, stripes):
     """hrs_encode_batch_host_multi: encode_batch_host over a device set
     (contiguous stripe ranges, one per codec, each on its own host thread)."""
     codes, arr = _codec_array(codes)
-    n = codes[0].stripeSize() + codes[0].paritySize()
-    sp, sshape, sstr = _host_ptr(stripes, "stripes", writable=True)
-    if len(sshape) != 3 or sshape[1] != n or sstr[2] != 1:
-        raise ValueError(f"stripes must be [S, {n}, L] with unit byte stride")
-    _lib.check(_lib.lib().hrs_encode_batch_host_multi(arr, len(codes), sp, sstr[1], sstr[0], sshape[2], sshape[0]),
-               codes[0]._h)
+    _encode_batch_host(codes[0], (arr, len(codes)), _lib.lib().hrs_encode_batch_host_multi, stripes)
 
 
 def apply_rows(code, matrix, in_rows, out_rows):
@@ -353,32 +378,88 @@ def crc32_rows(code, row_views, crc_in=None):
     returns an int32 tensor [S, nrows] holding the uint32 CRC bits
     (`& 0xFFFFFFFF` for the Java long value). crc_in, if given, is an int32
     tensor [S, nrows] of running CRCs to continue (CRC32.update chaining)."""
-    torch = _lib.torch
     rows, stride, L, S = _rows(row_views)
     ref = next(v for v in row_views if v is not None)
-    out = torch.empty((S, len(row_views)), dtype=torch.int32, device=ref.device)
-    cin = None
-    if crc_in is not None:
-        if crc_in.shape != out.shape or crc_in.dtype != torch.int32 or not crc_in.is_contiguous():
-            raise ValueError("crc_in must be a contiguous int32 tensor [S, nrows]")
-        cin = crc_in.data_ptr()
+    cin, out = _dev_crcs((S, len(row_views)), ref, L, S, crc_in)
     code._check(_lib.lib().hrs_crc32_dev(code._handle(), rows, len(row_views), stride, L, S, cin, out.data_ptr(),
                                          _stream(ref)))
     return out
 
+
+# ---- scrub, heal and heal with known erasures
 
 SCRUB_BAD, SCRUB_UNRESOLVED, SCRUB_FIRST_BAD, SCRUB_HEAD = 0, 1, 2, 4  # report words (include/hrs.h)
 SCRUB_PATCHED = 3  # heal only: bytes written back
 SCRUB_NONE = 0xFFFFFFFF
 
 
-def _scrub(code, rows, stride, L, S, ref, heal=False):
-    torch = _lib.torch
+def _dev_reports(code, L, S, ref):
+    """The int32 report tensor [S, 4 + n] of a device call, for the library to
+    fill; of a batch without bytes, filled here: every stripe is clean."""
     n = code.stripeSize() + code.paritySize()
-    reports = torch.empty((S, SCRUB_HEAD + n), dtype=torch.int32, device=ref.device)
-    call = _lib.lib().hrs_heal_dev if heal else _lib.lib().hrs_scrub_dev
-    code._check(call(code._handle(), rows, stride, L, S, reports.data_ptr(), SCRUB_HEAD + n, _stream(ref)))
+    reports = _lib.torch.empty((S, SCRUB_HEAD + n), dtype=_lib.torch.int32, device=ref.device)
+    if L == 0 or S == 0:
+        reports.zero_()
+        reports[:, SCRUB_FIRST_BAD] = -1
     return reports
+
+
+def _erased_array(erased, S, what="erased"):
+    """The host int32 [S, max_erased] erasure array of hrs_heal_erased_dev from
+    a [S, m] array or a list of per-stripe location lists (-1 padded)."""
+    torch = _lib.torch
+    if torch is not None and isinstance(erased, torch.Tensor):
+        erased = erased.cpu().numpy()
+    if isinstance(erased, np.ndarray):
+        arr = np.ascontiguousarray(erased.astype(np.int32))
+        if arr.ndim != 2 or arr.shape[0] != S:
+            raise ValueError(f"{what} must be [S, max_erased]")
+        return arr
+    lists = [list(e) for e in erased]
+    if len(lists) != S:
+        raise ValueError(f"{what} must list the erased locations of each of the {S} stripes")
+    arr = np.full((S, max(1, max(len(e) for e in lists))), -1, dtype=np.int32)
+    for s, e in enumerate(lists):
+        arr[s, : len(e)] = e
+    return arr
+
+
+def _scrub(code, batch, op, erased=None, crcs=None):
+    """hrs_<op>_dev or hrs_<op>_crc_dev over _code_stripes' or _code_rows'
+    tuple; op is "scrub", "heal" or, with `erased`, "heal_erased". Returns
+    the reports, with CRCs (reports, crcs)."""
+    rows, stride, L, S, ref = batch
+    args = [code._handle(), rows, stride, L, S]
+    if erased is not None:
+        arr = _erased_array(erased, S)
+        args += [arr.ctypes.data, arr.shape[1]]
+    reports = _dev_reports(code, L, S, ref)
+    args += [reports.data_ptr(), reports.shape[1]]
+    if crcs is None:
+        if L and S:
+            code._check(getattr(_lib.lib(), f"hrs_{op}_dev")(*args, _stream(ref)))
+        return reports
+    cin, crc = _dev_crcs((S, reports.shape[1] - SCRUB_HEAD), ref, L, S, *crcs)
+    if L and S:
+        code._check(getattr(_lib.lib(), f"hrs_{op}_crc_dev")(*args, cin, crc.data_ptr(), _stream(ref)))
+    return reports, crc
+
+
+def _scrub_batch_host(code, stripes, op, erased=None, crcs=None):
+    """hrs_<op>_batch_host or hrs_<op>_batch_host_crc; op and the result as for _scrub."""
+    sp, row_stride, stripe_stride, L, S = _host_batch(code, stripes, writable=op != "scrub")
+    args = [code._handle(), sp, row_stride, stripe_stride, L, S]
+    if erased is not None:
+        arr = _erased_array(erased, S)
+        args += [arr.ctypes.data, arr.shape[1]]
+    reports = np.zeros((S, SCRUB_HEAD + code.stripeSize() + code.paritySize()), dtype=np.uint32)
+    args += [reports.ctypes.data, reports.shape[1]]
+    if crcs is None:
+        code._check(getattr(_lib.lib(), f"hrs_{op}_batch_host")(*args))
+        return reports
+    cin, crc = _host_crcs((S, reports.shape[1] - SCRUB_HEAD), L, *crcs)
+    code._check(getattr(_lib.lib(), f"hrs_{op}_batch_host_crc")(*args, cin, crc.ctypes.data))
+    return reports, crc
 
 
 def scrub_stripes(code, stripes):
@@ -387,35 +468,19 @@ def scrub_stripes(code, stripes):
     uint32 report words of each stripe — bad columns, unresolved columns,
     first bad column (SCRUB_NONE if clean), 0, then per location the columns
     that resolved and blamed it."""
-    n = code.stripeSize() + code.paritySize()
-    if stripes.dim() != 3 or stripes.shape[1] != n:
-        raise ValueError(f"stripes must be [S, {n}, L]")
-    rows, stride, L, S = _stripe_rows(stripes, range(n))
-    return _scrub(code, rows, stride, L, S, stripes)
+    return _scrub(code, _code_stripes(code, stripes), "scrub")
 
 
 def scrub_rows(code, row_views):
     """scrub_stripes with explicit [S, L] row views, one per location in hops order."""
-    n = code.stripeSize() + code.paritySize()
-    if len(row_views) != n or any(v is None for v in row_views):
-        raise ValueError(f"need {n} row views")
-    rows, stride, L, S = _rows(row_views)
-    return _scrub(code, rows, stride, L, S, row_views[0])
+    return _scrub(code, _code_rows(code, row_views), "scrub")
 
 
 def scrub_batch_host(code, stripes):
     """hrs_scrub_batch_host: scrub_stripes for stripes[S, n, L] in HOST memory
     (numpy array or CPU tensor; pinned ones are read in place): a numpy uint32
     array [S, 4 + n]."""
-    n = code.stripeSize() + code.paritySize()
-    sp, sshape, sstr = _host_ptr(stripes, "stripes")
-    if len(sshape) != 3 or sshape[1] != n or sstr[2] != 1:
-        raise ValueError(f"stripes must be [S, {n}, L] with unit byte stride")
-    S, L = sshape[0], sshape[2]
-    reports = np.zeros((S, SCRUB_HEAD + n), dtype=np.uint32)
-    code._check(_lib.lib().hrs_scrub_batch_host(code._handle(), sp, sstr[1], sstr[0], L, S, reports.ctypes.data,
-                                                SCRUB_HEAD + n))
-    return reports
+    return _scrub_batch_host(code, stripes, "scrub")
 
 
 def heal_stripes(code, stripes):
@@ -424,20 +489,12 @@ def heal_stripes(code, stripes):
     post-call data, unresolved columns are left as they are. Returns the
     reports of the stripes as they were; word SCRUB_PATCHED counts the bytes
     stored."""
-    n = code.stripeSize() + code.paritySize()
-    if stripes.dim() != 3 or stripes.shape[1] != n:
-        raise ValueError(f"stripes must be [S, {n}, L]")
-    rows, stride, L, S = _stripe_rows(stripes, range(n))
-    return _scrub(code, rows, stride, L, S, stripes, heal=True)
+    return _scrub(code, _code_stripes(code, stripes), "heal")
 
 
 def heal_rows(code, row_views):
     """heal_stripes with explicit [S, L] row views, one per location in hops order."""
-    n = code.stripeSize() + code.paritySize()
-    if len(row_views) != n or any(v is None for v in row_views):
-        raise ValueError(f"need {n} row views")
-    rows, stride, L, S = _rows(row_views)
-    return _scrub(code, rows, stride, L, S, row_views[0], heal=True)
+    return _scrub(code, _code_rows(code, row_views), "heal")
 
 
 def heal_batch_host(code, stripes):
@@ -445,15 +502,7 @@ def heal_batch_host(code, stripes):
     (numpy array or CPU tensor, healed in place; of staged memory only the
     cells that held a resolved error are written): a numpy uint32 array
     [S, 4 + n]."""
-    n = code.stripeSize() + code.paritySize()
-    sp, sshape, sstr = _host_ptr(stripes, "stripes", writable=True)
-    if len(sshape) != 3 or sshape[1] != n or sstr[2] != 1:
-        raise ValueError(f"stripes must be [S, {n}, L] with unit byte stride")
-    S, L = sshape[0], sshape[2]
-    reports = np.zeros((S, SCRUB_HEAD + n), dtype=np.uint32)
-    code._check(_lib.lib().hrs_heal_batch_host(code._handle(), sp, sstr[1], sstr[0], L, S, reports.ctypes.data,
-                                               SCRUB_HEAD + n))
-    return reports
+    return _scrub_batch_host(code, stripes, "heal")
 
 
 def heal_host(code, rows):
@@ -479,36 +528,6 @@ def _host_stripe_rows(rows, n):
     return len(rows[0])
 
 
-def _erased_array(erased, S, what="erased"):
-    """The host int32 [S, max_erased] erasure array of hrs_heal_erased_dev from
-    a [S, m] array or a list of per-stripe location lists (-1 padded)."""
-    torch = _lib.torch
-    if torch is not None and isinstance(erased, torch.Tensor):
-        erased = erased.cpu().numpy()
-    if isinstance(erased, np.ndarray):
-        arr = np.ascontiguousarray(erased.astype(np.int32))
-        if arr.ndim != 2 or arr.shape[0] != S:
-            raise ValueError(f"{what} must be [S, max_erased]")
-        return arr
-    lists = [list(e) for e in erased]
-    if len(lists) != S:
-        raise ValueError(f"{what} must list the erased locations of each of the {S} stripes")
-    arr = np.full((S, max(1, max(len(e) for e in lists))), -1, dtype=np.int32)
-    for s, e in enumerate(lists):
-        arr[s, : len(e)] = e
-    return arr
-
-
-def _heal_erased(code, rows, stride, L, S, ref, erased):
-    torch = _lib.torch
-    n = code.stripeSize() + code.paritySize()
-    arr = _erased_array(erased, S)
-    reports = torch.empty((S, SCRUB_HEAD + n), dtype=torch.int32, device=ref.device)
-    code._check(_lib.lib().hrs_heal_erased_dev(code._handle(), rows, stride, L, S, arr.ctypes.data, arr.shape[1],
-                                               reports.data_ptr(), SCRUB_HEAD + n, _stream(ref)))
-    return reports
-
-
 def heal_erased_stripes(code, stripes, erased):
     """Heal with known erasures (hrs_heal_erased_dev) over stripes[S, n, L]:
     per stripe the lost cells erased[s] (an int [S, m] array, -1 padded, e.g.
@@ -519,20 +538,12 @@ def heal_erased_stripes(code, stripes, erased):
     heal's layout: columns whose survivors disagree, unresolved columns, first
     bad column, survivor bytes stored, then per survivor the resolved columns
     that blamed it."""
-    n = code.stripeSize() + code.paritySize()
-    if stripes.dim() != 3 or stripes.shape[1] != n:
-        raise ValueError(f"stripes must be [S, {n}, L]")
-    rows, stride, L, S = _stripe_rows(stripes, range(n))
-    return _heal_erased(code, rows, stride, L, S, stripes, erased)
+    return _scrub(code, _code_stripes(code, stripes), "heal_erased", erased)
 
 
 def heal_erased_rows(code, row_views, erased):
     """heal_erased_stripes with explicit [S, L] row views, one per location in hops order."""
-    n = code.stripeSize() + code.paritySize()
-    if len(row_views) != n or any(v is None for v in row_views):
-        raise ValueError(f"need {n} row views")
-    rows, stride, L, S = _rows(row_views)
-    return _heal_erased(code, rows, stride, L, S, row_views[0], erased)
+    return _scrub(code, _code_rows(code, row_views), "heal_erased", erased)
 
 
 def heal_erased_host(code, rows, erased):
@@ -549,26 +560,6 @@ def heal_erased_host(code, rows, erased):
     return report
 
 
-def _heal_erased_crc(code, rows, stride, L, S, ref, erased, crc_in):
-    torch = _lib.torch
-    n = code.stripeSize() + code.paritySize()
-    arr = _erased_array(erased, S)
-    reports = torch.empty((S, SCRUB_HEAD + n), dtype=torch.int32, device=ref.device)
-    crc = torch.empty((S, n), dtype=torch.int32, device=ref.device)
-    cin = None
-    if crc_in is not None:
-        if crc_in.shape != crc.shape or crc_in.dtype != torch.int32 or not crc_in.is_contiguous() \
-                or crc_in.device != ref.device:
-            raise ValueError(f"crc_in must be a contiguous int32 device tensor [S, {n}]")
-        cin = crc_in.data_ptr()
-    if L == 0 or S == 0:  # the call touches nothing: every CRC continues over no bytes
-        crc.zero_() if crc_in is None else crc.copy_(crc_in)
-    code._check(_lib.lib().hrs_heal_erased_crc_dev(code._handle(), rows, stride, L, S, arr.ctypes.data, arr.shape[1],
-                                                   reports.data_ptr(), SCRUB_HEAD + n, cin, crc.data_ptr(),
-                                                   _stream(ref)))
-    return reports, crc
-
-
 def heal_erased_stripes_crc(code, stripes, erased, crc_in=None):
     """heal_erased_stripes plus the CRC-32 of every cell AS THE CALL LEAVES IT
     (hrs_heal_erased_crc_dev): rebuilt cells, patched survivors, unresolved
@@ -576,39 +567,12 @@ def heal_erased_stripes_crc(code, stripes, erased, crc_in=None):
     of the uint32 CRC bits in HOPS order as heal_stripes_crc returns them;
     crc_in ([S, n] int32) continues running CRCs. A stripe whose CRCs equal its
     stored checksums was restored."""
-    n = code.stripeSize() + code.paritySize()
-    if stripes.dim() != 3 or stripes.shape[1] != n:
-        raise ValueError(f"stripes must be [S, {n}, L]")
-    rows, stride, L, S = _stripe_rows(stripes, range(n))
-    return _heal_erased_crc(code, rows, stride, L, S, stripes, erased, crc_in)
+    return _scrub(code, _code_stripes(code, stripes), "heal_erased", erased, (crc_in,))
 
 
 def heal_erased_rows_crc(code, row_views, erased, crc_in=None):
     """heal_erased_stripes_crc with explicit [S, L] row views, one per location in hops order."""
-    n = code.stripeSize() + code.paritySize()
-    if len(row_views) != n or any(v is None for v in row_views):
-        raise ValueError(f"need {n} row views")
-    rows, stride, L, S = _rows(row_views)
-    return _heal_erased_crc(code, rows, stride, L, S, row_views[0], erased, crc_in)
-
-
-def _heal_erased_batch_host(code, stripes, erased, with_crc, crc_in=None, crc_out=None):
-    n = code.stripeSize() + code.paritySize()
-    sp, sshape, sstr = _host_ptr(stripes, "stripes", writable=True)
-    if len(sshape) != 3 or sshape[1] != n or sstr[2] != 1:
-        raise ValueError(f"stripes must be [S, {n}, L] with unit byte stride")
-    S, L = sshape[0], sshape[2]
-    arr = _erased_array(erased, S)
-    reports = np.zeros((S, SCRUB_HEAD + n), dtype=np.uint32)
-    if not with_crc:
-        code._check(_lib.lib().hrs_heal_erased_batch_host(code._handle(), sp, sstr[1], sstr[0], L, S, arr.ctypes.data,
-                                                          arr.shape[1], reports.ctypes.data, SCRUB_HEAD + n))
-        return reports
-    cin, crc = _host_crcs((S, n), L, crc_in, crc_out)
-    code._check(_lib.lib().hrs_heal_erased_batch_host_crc(code._handle(), sp, sstr[1], sstr[0], L, S, arr.ctypes.data,
-                                                          arr.shape[1], reports.ctypes.data, SCRUB_HEAD + n, cin,
-                                                          crc.ctypes.data))
-    return reports, crc
+    return _scrub(code, _code_rows(code, row_views), "heal_erased", erased, (crc_in,))
 
 
 def heal_erased_batch_host(code, stripes, erased):
@@ -617,14 +581,14 @@ def heal_erased_batch_host(code, stripes, erased):
     only the survivors are copied in, and only the erased cells and the cells
     that held a resolved error are written): a numpy uint32 array [S, 4 + n].
     erased as for heal_erased_stripes."""
-    return _heal_erased_batch_host(code, stripes, erased, False)
+    return _scrub_batch_host(code, stripes, "heal_erased", erased)
 
 
 def heal_erased_batch_host_crc(code, stripes, erased, crc_in=None, crc_out=None):
     """hrs_heal_erased_batch_host_crc: heal_erased_batch_host plus the CRC-32
     of every cell as the call leaves it: (reports, crcs), crcs a numpy uint32
     array [S, n] in HOPS order; crc_in and crc_out as for heal_batch_host_crc."""
-    return _heal_erased_batch_host(code, stripes, erased, True, crc_in, crc_out)
+    return _scrub_batch_host(code, stripes, "heal_erased", erased, (crc_in, crc_out))
 
 
 def scrub_to_erased(reports, p):
@@ -650,79 +614,30 @@ def scrub_to_erased(reports, p):
     return erased
 
 
-def _scrub_crc(code, rows, stride, L, S, ref, crc_in, heal):
-    torch = _lib.torch
-    n = code.stripeSize() + code.paritySize()
-    reports = torch.empty((S, SCRUB_HEAD + n), dtype=torch.int32, device=ref.device)
-    crc = torch.empty((S, n), dtype=torch.int32, device=ref.device)
-    cin = None
-    if crc_in is not None:
-        if crc_in.shape != crc.shape or crc_in.dtype != torch.int32 or not crc_in.is_contiguous() \
-                or crc_in.device != ref.device:
-            raise ValueError(f"crc_in must be a contiguous int32 device tensor [S, {n}]")
-        cin = crc_in.data_ptr()
-    if L == 0 or S == 0:  # the call touches nothing: every CRC continues over no bytes
-        crc.zero_() if crc_in is None else crc.copy_(crc_in)
-    call = _lib.lib().hrs_heal_crc_dev if heal else _lib.lib().hrs_scrub_crc_dev
-    code._check(call(code._handle(), rows, stride, L, S, reports.data_ptr(), SCRUB_HEAD + n, cin, crc.data_ptr(),
-                     _stream(ref)))
-    return reports, crc
-
-
 def scrub_stripes_crc(code, stripes, crc_in=None):
     """scrub_stripes plus the CRC-32 (java.util.zip.CRC32) of every cell from
     the same read (hrs_scrub_crc_dev): returns (reports, crcs), crcs an int32
     tensor [S, n] of the uint32 CRC bits in HOPS order (column l = location l,
     parity first; not encode_stripes_crc's data-first order), as crc32_rows
     returns it over the n rows. crc_in ([S, n] int32) continues running CRCs."""
-    n = code.stripeSize() + code.paritySize()
-    if stripes.dim() != 3 or stripes.shape[1] != n:
-        raise ValueError(f"stripes must be [S, {n}, L]")
-    rows, stride, L, S = _stripe_rows(stripes, range(n))
-    return _scrub_crc(code, rows, stride, L, S, stripes, crc_in, False)
+    return _scrub(code, _code_stripes(code, stripes), "scrub", None, (crc_in,))
 
 
 def scrub_rows_crc(code, row_views, crc_in=None):
     """scrub_stripes_crc with explicit [S, L] row views, one per location in hops order."""
-    n = code.stripeSize() + code.paritySize()
-    if len(row_views) != n or any(v is None for v in row_views):
-        raise ValueError(f"need {n} row views")
-    rows, stride, L, S = _rows(row_views)
-    return _scrub_crc(code, rows, stride, L, S, row_views[0], crc_in, False)
+    return _scrub(code, _code_rows(code, row_views), "scrub", None, (crc_in,))
 
 
 def heal_stripes_crc(code, stripes, crc_in=None):
     """heal_stripes plus the CRC-32 of every cell AS IT IS AFTER the write-back
     (hrs_heal_crc_dev): (reports, crcs) as for scrub_stripes_crc. A cell whose
     CRC equals its stored checksum was restored."""
-    n = code.stripeSize() + code.paritySize()
-    if stripes.dim() != 3 or stripes.shape[1] != n:
-        raise ValueError(f"stripes must be [S, {n}, L]")
-    rows, stride, L, S = _stripe_rows(stripes, range(n))
-    return _scrub_crc(code, rows, stride, L, S, stripes, crc_in, True)
+    return _scrub(code, _code_stripes(code, stripes), "heal", None, (crc_in,))
 
 
 def heal_rows_crc(code, row_views, crc_in=None):
     """heal_stripes_crc with explicit [S, L] row views, one per location in hops order."""
-    n = code.stripeSize() + code.paritySize()
-    if len(row_views) != n or any(v is None for v in row_views):
-        raise ValueError(f"need {n} row views")
-    rows, stride, L, S = _rows(row_views)
-    return _scrub_crc(code, rows, stride, L, S, row_views[0], crc_in, True)
-
-
-def _scrub_batch_host_crc(code, stripes, crc_in, crc_out, heal):
-    n = code.stripeSize() + code.paritySize()
-    sp, sshape, sstr = _host_ptr(stripes, "stripes", writable=heal)
-    if len(sshape) != 3 or sshape[1] != n or sstr[2] != 1:
-        raise ValueError(f"stripes must be [S, {n}, L] with unit byte stride")
-    S, L = sshape[0], sshape[2]
-    cin, crc = _host_crcs((S, n), L, crc_in, crc_out)
-    reports = np.zeros((S, SCRUB_HEAD + n), dtype=np.uint32)
-    call = _lib.lib().hrs_heal_batch_host_crc if heal else _lib.lib().hrs_scrub_batch_host_crc
-    code._check(call(code._handle(), sp, sstr[1], sstr[0], L, S, reports.ctypes.data, SCRUB_HEAD + n, cin,
-                     crc.ctypes.data))
-    return reports, crc
+    return _scrub(code, _code_rows(code, row_views), "heal", None, (crc_in,))
 
 
 def scrub_batch_host_crc(code, stripes, crc_in=None, crc_out=None):
@@ -730,13 +645,13 @@ def scrub_batch_host_crc(code, stripes, crc_in=None, crc_out=None):
     from the same read: (reports, crcs), crcs a numpy uint32 array [S, n] in
     HOPS order. crc_in (same layout) continues running CRCs; crc_out: the array
     to fill and return (it may be crc_in itself)."""
-    return _scrub_batch_host_crc(code, stripes, crc_in, crc_out, False)
+    return _scrub_batch_host(code, stripes, "scrub", None, (crc_in, crc_out))
 
 
 def heal_batch_host_crc(code, stripes, crc_in=None, crc_out=None):
     """hrs_heal_batch_host_crc: heal_batch_host plus the CRC-32 of every cell as
     it is after the write-back; arguments and result as scrub_batch_host_crc."""
-    return _scrub_batch_host_crc(code, stripes, crc_in, crc_out, True)
+    return _scrub_batch_host(code, stripes, "heal", None, (crc_in, crc_out))
 
 
 def checksums_to_erased(crcs, stored, p, reports=None):
@@ -788,7 +703,8 @@ REPAIR_CLEAN, REPAIR_REPAIRED, REPAIR_RESTAMP, REPAIR_FAILED, REPAIR_TOOMANY, RE
 REPAIR_JOIN_SYNDROMES = 1
 
 
-def _repair_checked(code, rows, stride, L, S, ref, stored, join_syndromes):
+def _repair_checked(code, batch, stored, join_syndromes):
+    rows, stride, L, S, ref = batch
     torch = _lib.torch
     n, p = code.stripeSize() + code.paritySize(), code.paritySize()
     if (not isinstance(stored, torch.Tensor) or stored.shape != (S, n) or stored.dtype != torch.int32
@@ -796,14 +712,13 @@ def _repair_checked(code, rows, stride, L, S, ref, stored, join_syndromes):
         raise ValueError(f"stored must be a contiguous int32 device tensor [S, {n}]")
     verdicts = torch.empty((S,), dtype=torch.int32, device=ref.device)
     erased = torch.empty((S, p), dtype=torch.int32, device=ref.device)
-    reports = torch.empty((S, SCRUB_HEAD + n), dtype=torch.int32, device=ref.device)
+    reports = _dev_reports(code, L, S, ref)
     crcs = torch.empty((S, n), dtype=torch.int32, device=ref.device)
     if L == 0 or S == 0:  # the call touches nothing: every stripe is clean, every CRC is over no bytes
         verdicts.zero_()
         erased.fill_(-1)
-        reports.zero_()
-        reports[:, SCRUB_FIRST_BAD] = -1
         crcs.zero_()
+        return verdicts, erased, reports, crcs
     code._check(_lib.lib().hrs_repair_checked_dev(
         code._handle(), rows, stride, L, S, stored.data_ptr(), REPAIR_JOIN_SYNDROMES if join_syndromes else 0,
         verdicts.data_ptr(), erased.data_ptr(), reports.data_ptr(), SCRUB_HEAD + n, crcs.data_ptr(), _stream(ref)))
@@ -827,20 +742,12 @@ def repair_checked_stripes(code, stripes, stored, join_syndromes=False):
     whole-cell garbage makes the locator blame sound cells. Returns device
     tensors (verdicts [S], erased [S, p] ascending and -1 padded, reports
     [S, 4 + n], crcs [S, n]), all int32."""
-    n = code.stripeSize() + code.paritySize()
-    if stripes.dim() != 3 or stripes.shape[1] != n:
-        raise ValueError(f"stripes must be [S, {n}, L]")
-    rows, stride, L, S = _stripe_rows(stripes, range(n))
-    return _repair_checked(code, rows, stride, L, S, stripes, stored, join_syndromes)
+    return _repair_checked(code, _code_stripes(code, stripes), stored, join_syndromes)
 
 
 def repair_checked_rows(code, row_views, stored, join_syndromes=False):
     """repair_checked_stripes with explicit [S, L] row views, one per location in hops order."""
-    n = code.stripeSize() + code.paritySize()
-    if len(row_views) != n or any(v is None for v in row_views):
-        raise ValueError(f"need {n} row views")
-    rows, stride, L, S = _rows(row_views)
-    return _repair_checked(code, rows, stride, L, S, row_views[0], stored, join_syndromes)
+    return _repair_checked(code, _code_rows(code, row_views), stored, join_syndromes)
 
 
 def repair_checked_host(code, rows, stored, join_syndromes=False):
