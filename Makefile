@@ -13,7 +13,8 @@ HDRS     := Makefile include/hrs.h lambdafs_amd/csrc/hrs_device.hpp lambdafs_amd
             lambdafs_amd/csrc/crc32.hpp lambdafs_amd/csrc/hrs_crc.hpp lambdafs_amd/csrc/xor_sched.hpp lambdafs_amd/csrc/hrs_codec.hpp \
             lambdafs_amd/csrc/hrs_host.hpp lambdafs_amd/csrc/hrs_locator.hpp lambdafs_amd/csrc/hrs_heal_erased.hpp \
             lambdafs_amd/csrc/hrs_heal_erased_device.hpp \
-            lambdafs_amd/csrc/hrs_scrub_device.hpp lambdafs_amd/csrc/hrs_repair.hpp lambdafs_amd/csrc/hrs_repair_rule.hpp
+            lambdafs_amd/csrc/hrs_scrub_device.hpp lambdafs_amd/csrc/hrs_repair.hpp lambdafs_amd/csrc/hrs_repair_rule.hpp \
+            lambdafs_amd/csrc/hrs_ragged.hpp
 
 # Host translation units of the C ABI (no kernels): lifecycle + queries,
 # matrices, device dispatch, the CRC-32 service, host-buffer path, repair
@@ -60,7 +61,7 @@ build/hrs_fused.o: HIPFLAGS += -mllvm -pragma-unroll-threshold=1000000
 build/hrs_probe.o: include/hrs_probe.h
 
 # `make scrub_resources`, `make scrub_crc_resources`, `make heal_erased_resources`,
-# `make heal_erased_crc_resources`, `make repair_resources`:
+# `make heal_erased_crc_resources`, `make repair_resources`, `make ragged_resources`:
 # the compiler's resource report of every kernel of hrs_<name>.hip (the scrub
 # family carries no scratch). Not .PHONY: a phony target takes no pattern rule.
 %_resources: lambdafs_amd/csrc/hrs_%.hip $(HDRS)
@@ -70,7 +71,7 @@ build/hrs_probe.o: include/hrs_probe.h
 
 KOBJ     := build/hrs_kernels.o build/hrs_runtime.o build/hrs_batch.o build/hrs_crc.o build/hrs_fused.o build/hrs_decode_crc.o \
             build/hrs_batch_crc.o build/hrs_scrub.o build/hrs_scrub_crc.o build/hrs_heal_erased.o \
-            build/hrs_heal_erased_crc.o build/hrs_repair.o
+            build/hrs_heal_erased_crc.o build/hrs_repair.o build/hrs_ragged.o
 
 $(LIB): $(API_OBJ) $(KOBJ) lambdafs_amd/csrc/libhrs.map
 	$(HIPCC) $(HIPFLAGS) -shared -Wl,--version-script=lambdafs_amd/csrc/libhrs.map -o $@ $(API_OBJ) $(KOBJ) \

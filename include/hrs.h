@@ -466,6 +466,66 @@ hrs_status hrs_decode_batch_host_crc(hrs_codec* codec, const uint8_t* stripes, s
 hrs_status hrs_encode_batch_host_crc(hrs_codec* codec, uint8_t* stripes, size_t row_stride, size_t stripe_stride,
                                      size_t len, size_t nstripes, const uint32_t* crc_in, uint32_t* crc_out);
 
+/* ---- ragged encode: per-cell valid lengths, zero tails never read ----
+ * Every file ends in a stripe that is not full. Where the reference has no
+ * source bytes for a cell it feeds zeros and reads nothing: a ZeroInputStream
+ * for every block past the end of the file (FileStripeReader.java:56-67,
+ * :96-104; StripeReader.java:111-120), and RaidUtils.readTillEnd zero-fills
+ * the rest of a buffer at EOF and returns the bytes it really read
+ * (RaidUtils.java:45-80), which ParallelStreamReader.ReadResult.numRead carries
+ * per stream (ParallelStreamReader.java:54-64, :236-249) to
+ * Encoder.encodeStripe (Encoder.java:437-442). A ragged batch is an ordinary
+ * encode batch plus that count:
+ *   - valid is a HOST array of uint32_t[nstripes * k];
+ *   - valid[s * k + j] is the number of leading bytes of data cell j of stripe
+ *     s (hops location p + j) that hold data;
+ *   - the cell is taken to be those bytes followed by len - valid zeros,
+ *     exactly the buffer readTillEnd hands encodeBulk.
+ * The calls guarantee:
+ *   - parity is bit-exact with encodeBulk over the zero-filled cells, for every
+ *     code family a handle can have (rs, nrs, xor, src);
+ *   - bytes of a cell at or beyond valid never influence any output, whatever
+ *     they hold;
+ *   - the storage of the whole cell (len bytes) must still be addressable;
+ *   - the vector kernel loads no 2 KiB window that lies wholly at or beyond
+ *     valid; the one window that contains the boundary is loaded and masked;
+ *   - the staged host path copies in no byte at or beyond valid;
+ *   - data cells are never written; parity rows are fully written.
+ * Argument rules, in this order: a NULL handle is HRS_EINVAL with no message;
+ * a NULL pointer argument, valid included, is HRS_EINVAL (a caller with full
+ * stripes uses the plain call); len == 0 or nstripes == 0 returns HRS_OK and
+ * touches nothing; len > UINT32_MAX or a valid entry > len is HRS_EINVAL with
+ * the stripe and row named, and so is a NULL row pointer; only then the device
+ * is selected (HRS_EDEVICE for a host-only handle). Argument errors come
+ * before any byte is copied.
+ * Kernels: rs (3,2), (6,3), (10,4), (12,4) and nrs (10,4), (6,3) with 16-byte
+ * aligned rows and strides take encode_ragged_kernel<K, P> over the whole
+ * 2 KiB windows; the row tail, unaligned layouts, kernel mode 2 and every
+ * other code or shape take encode_ragged_bytewise_kernel (hrs_last_kernel
+ * names them by the plain encode's tail rule). A batch whose every entry
+ * equals len runs the plain encode itself and hrs_last_kernel names that
+ * kernel, so always calling the ragged form costs nothing (kernel modes 2 and
+ * 3 keep the ragged kernels even then; hrs_set_kernel_mode).
+ * Not covered, by design: the synchronous single-stripe host call and its JNI
+ * overload, the CRC forms (the CRC of a zero tail is an advance by Z_len),
+ * ragged survivors in the repair calls. */
+
+/* hrs_encode_dev's rows and layout plus valid. Asynchronous on stream; valid
+ * is copied before the call returns (through the handle's per-call table
+ * slots) and may be reused at once. */
+hrs_status hrs_encode_ragged_dev(hrs_codec* codec, const uint8_t* const* in_rows, size_t in_stride,
+                                 uint8_t* const* out_rows, size_t out_stride, size_t len, size_t nstripes,
+                                 const uint32_t* valid, void* stream);
+
+/* hrs_encode_batch_host's layout plus valid, in place. Runtime-pinned stripes
+ * run as one zero-copy launch: dead windows never cross the host link. Any
+ * other memory is staged through the host-batch pipeline with only the valid
+ * bytes of each data cell copied in (and, with HRS_ZEROCOPY=0, sent to the
+ * device). hrs_last_host_path as for hrs_encode_batch_host, set only on
+ * success. Synchronous. */
+hrs_status hrs_encode_ragged_batch_host(hrs_codec* codec, uint8_t* stripes, size_t row_stride, size_t stripe_stride,
+                                        size_t len, size_t nstripes, const uint32_t* valid);
+
 /* ---- stripe scrubbing: ReedSolomonCode.computeErrorLocations in bulk ----
  * Whether a stripe at rest is still a codeword, and which cells went bad when
  * nothing reported an erasure. For each byte column c of each stripe the
@@ -840,7 +900,12 @@ hrs_status hrs_repair_checked_host(const hrs_codec* codec, uint8_t* const* rows,
 /* Kernel selection for tests and benchmarks: 0 = auto (default), 1 = force
  * the runtime-matrix bit-sliced kernel, 2 = force the byte-granular kernel,
  * 3 = auto, except that hrs_encode_crc_dev and the heal-with-erasures + CRC
- * calls take their fused kernel whenever the shape allows it. */
+ * calls take their fused kernel whenever the shape allows it.
+ * The ragged encode calls: 0 and 1 send a batch whose every valid entry equals
+ * len to the plain encode (which then follows its own mode) and any other
+ * batch to the ragged kernels, vector where the shape has one; 2 forces
+ * encode_ragged_bytewise_kernel for every batch; 3 keeps the ragged kernels
+ * for an all-full batch too (tests and benchmarks). */
 hrs_status hrs_set_kernel_mode(hrs_codec* codec, int mode);
 
 #ifdef __cplusplus

@@ -228,6 +228,19 @@ class HipCode : public ErasureCode {
     check(hrs_encode_batch_host_crc(h_, stripes, rowStride, stripeStride, len, nstripes, crcIn, crcOut), h_);
   }
 
+  // The ragged encode (hrs_encode_ragged_dev, hrs_encode_ragged_batch_host;
+  // semantics in include/hrs.h): valid[s * k + j] leading bytes of data cell
+  // j of stripe s hold data, the rest reads as zeros and is never read.
+  void encodeRaggedDev(const uint8_t* const* inRows, size_t inStride, uint8_t* const* outRows, size_t outStride,
+                       size_t len, size_t nstripes, const uint32_t* valid, void* stream) {
+    check(hrs_encode_ragged_dev(h_, inRows, inStride, outRows, outStride, len, nstripes, valid, stream), h_);
+  }
+
+  void encodeRaggedBatchHost(uint8_t* stripes, size_t rowStride, size_t stripeStride, size_t len, size_t nstripes,
+                             const uint32_t* valid) {
+    check(hrs_encode_ragged_batch_host(h_, stripes, rowStride, stripeStride, len, nstripes, valid), h_);
+  }
+
   // RS-specific decodeBulk(readBufs, writeBufs, erasedLocation), ReedSolomonCode.java:168-185.
   void decodeBulk3(const std::vector<uint8_t*>& readBufs, const std::vector<uint8_t*>& writeBufs, size_t len,
                    const std::vector<int>& erased) {

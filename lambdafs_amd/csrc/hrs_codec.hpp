@@ -216,6 +216,23 @@ hrs_status run_apply(hrs_codec* c, const uint8_t* m, int nout, int nin, const ui
                      size_t in_stride, uint8_t* const* out_rows, size_t out_stride, size_t len, size_t nstripes,
                      hipStream_t s, bool static_kp);
 
+// ---- ragged encode (hrs_dispatch.cpp; kernels: hrs_ragged.hip)
+// Rule 4 of the ragged entry points (include/hrs.h): len <= UINT32_MAX and
+// every one of the nstripes * k HOST words of `valid` <= len, the stripe and
+// row named. *all_full: every word equals len.
+hrs_status ragged_valid_ok(hrs_codec* c, const uint32_t* valid, size_t len, size_t nstripes, bool* all_full);
+// Whether a ragged batch takes the plain encode: every cell full, and the
+// kernel mode does not pin the ragged kernels (2, 3).
+inline bool ragged_takes_plain(const hrs_codec* c, bool all_full) {
+  return all_full && c->kernel_mode != 2 && c->kernel_mode != 3;
+}
+// encodeBulk over data cells that read as zero from dvalid[s * k + j] on
+// (DEVICE words, at the range's first stripe): the vector kernel over the
+// whole 2 KiB windows of aligned rows of a static shape, the byte-granular
+// kernel over the rest. in_rows[k], out_rows[p]: none NULL. len, nstripes > 0.
+hrs_status run_ragged(hrs_codec* c, const uint8_t* const* in_rows, size_t in_stride, uint8_t* const* out_rows,
+                      size_t out_stride, size_t len, size_t nstripes, const uint32_t* dvalid, hipStream_t s);
+
 // ---- CRC-32 (hrs_crc_api.cpp)
 size_t crc_raw_bytes_for(size_t len, size_t nstripes, int nrows);
 hrs_status run_crc(hrs_codec* c, const uint8_t* const* rows, const size_t* strides, int nrows, size_t len,

@@ -1,7 +1,8 @@
 // Device-resident dispatch: the matrix-apply planner that picks a gfx950
 // kernel per shape (static encode, XOR, resident / pipelined / streaming
-// runtime kernels, byte-granular tails), and the hrs_encode_dev,
-// hrs_decode_dev and hrs_apply_dev entry points.
+// runtime kernels, byte-granular tails), the ragged encode's planner, and the
+// hrs_encode_dev, hrs_encode_ragged_dev, hrs_decode_dev and hrs_apply_dev
+// entry points.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -12,6 +13,7 @@
 #include "../../include/hrs.h"
 #include "hrs_codec.hpp"
 #include "hrs_internal.hpp"
+#include "hrs_ragged.hpp"
 
 namespace hrs::api {
 
@@ -185,6 +187,84 @@ hrs_status run_apply(hrs_codec* c, const uint8_t* m, int nout, int nin, const ui
   return HRS_OK;
 }
 
+hrs_status ragged_valid_ok(hrs_codec* c, const uint32_t* valid, size_t len, size_t nstripes, bool* all_full) {
+  if (len > UINT32_MAX) return fail(c, HRS_EINVAL, "ragged encode: len %zu exceeds 2^32 - 1", len);
+  const size_t k = static_cast<size_t>(c->k);
+  bool full = true;
+  for (size_t s = 0; s < nstripes; ++s)
+    for (size_t j = 0; j < k; ++j) {
+      const uint32_t v = valid[s * k + j];
+      if (v > len) return fail(c, HRS_EINVAL, "stripe %zu row %zu: valid %u exceeds len %zu", s, j, v, len);
+      full &= v == len;
+    }
+  *all_full = full;
+  return HRS_OK;
+}
+
+hrs_status run_ragged(hrs_codec* c, const uint8_t* const* in_rows, size_t in_stride, uint8_t* const* out_rows,
+                      size_t out_stride, size_t len, size_t nstripes, const uint32_t* dvalid, hipStream_t s) {
+  const int k = c->k, p = c->p;
+  bool vec_ok = c->kernel_mode != 2 && static_encode_family(c) && k <= hrs::kMaxIn && p <= hrs::kMaxOut &&
+                in_stride % 16 == 0 && out_stride % 16 == 0;
+  for (int i = 0; i < k && vec_ok; ++i) vec_ok = aligned16(in_rows[i]);
+  for (int o = 0; o < p && vec_ok; ++o) vec_ok = aligned16(out_rows[o]);
+  uint64_t col0 = 0;  // columns the vector kernel has covered
+  const uint64_t nwin = vec_ok ? len / hrs::kWindowBytes : 0;
+  if (nwin > 0) {
+    hrs::RaggedArgs a{};
+    for (int i = 0; i < k; ++i) a.r.in[i] = in_rows[i];
+    for (int o = 0; o < p; ++o) a.r.out[o] = out_rows[o];
+    a.r.in_stride = in_stride;
+    a.r.out_stride = out_stride;
+    a.r.len = len;
+    a.r.nwin = nwin;
+    a.r.ntasks = nwin * nstripes;
+    a.r.nin = k;
+    a.r.nout = p;
+    a.valid = dvalid;
+    a.k = k;
+    bool handled = false;
+    const int family = c->kind == HRS_CODE_NRS ? hrs::kStaticCauchy : hrs::kStaticRs;
+    const hipError_t e = hrs::launch_ragged_encode(family, k, p, a, s, &handled);
+    if (e != hipSuccess) return hip_fail(c, e, "ragged encode launch");
+    if (handled) {
+      c->last_kernel = hrs::last_kernel();
+      col0 = nwin * hrs::kWindowBytes;
+    }
+  }
+  if (col0 == len) return HRS_OK;
+  // the byte-granular kernel over columns [col0, len): outputs in chunks of
+  // kMaxOut, inputs in chunks of kMaxIn (later chunks accumulate)
+  const uint8_t* m = c->g.data();
+  for (int o0 = 0; o0 < p; o0 += hrs::kMaxOut) {
+    const int no = std::min(hrs::kMaxOut, p - o0);
+    for (int i0 = 0; i0 < k; i0 += hrs::kMaxIn) {
+      const int ni = std::min(hrs::kMaxIn, k - i0);
+      hrs::RaggedArgs b{};
+      for (int i = 0; i < ni; ++i) b.r.in[i] = in_rows[i0 + i];
+      for (int o = 0; o < no; ++o) {
+        b.r.out[o] = out_rows[o0 + o];
+        for (int i = 0; i < ni; ++i) hrs::set_coef(b.r, o, i, m[(o0 + o) * k + i0 + i]);
+      }
+      b.r.in_stride = in_stride;
+      b.r.out_stride = out_stride;
+      b.r.len = len;
+      b.r.ntasks = (len - col0) * nstripes;
+      b.r.nin = ni;
+      b.r.nout = no;
+      b.r.accumulate = i0 > 0;
+      b.valid = dvalid;
+      b.col0 = col0;
+      b.k = k;
+      b.row0 = i0;
+      const hipError_t e = hrs::launch_ragged_bytewise(b, s);
+      if (e != hipSuccess) return hip_fail(c, e, "ragged bytewise launch");
+      if (col0 == 0) c->last_kernel = hrs::last_kernel();  // the call's only kernel
+    }
+  }
+  return HRS_OK;
+}
+
 }  // namespace hrs::api
 
 using namespace hrs::api;
@@ -199,6 +279,34 @@ hrs_status hrs_encode_dev(hrs_codec* c, const uint8_t* const* in_rows, size_t in
   if (!g.ok) return fail(c, HRS_EDEVICE, "cannot select HIP device %d", c->device);
   return run_apply(c, c->g.data(), c->p, c->k, in_rows, in_stride, out_rows, out_stride, len, nstripes,
                    static_cast<hipStream_t>(stream), static_encode_family(c));
+}
+
+hrs_status hrs_encode_ragged_dev(hrs_codec* c, const uint8_t* const* in_rows, size_t in_stride,
+                                 uint8_t* const* out_rows, size_t out_stride, size_t len, size_t nstripes,
+                                 const uint32_t* valid, void* stream) {
+  if (!c) return HRS_EINVAL;
+  if (!in_rows || !out_rows || !valid) return fail(c, HRS_EINVAL, "row arrays or valid are NULL");
+  if (len == 0 || nstripes == 0) return HRS_OK;
+  bool all_full = false;
+  hrs_status st = ragged_valid_ok(c, valid, len, nstripes, &all_full);
+  if (st != HRS_OK) return st;
+  for (int i = 0; i < c->k; ++i)
+    if (!in_rows[i]) return fail(c, HRS_EINVAL, "input row %d is NULL", i);
+  for (int o = 0; o < c->p; ++o)
+    if (!out_rows[o]) return fail(c, HRS_EINVAL, "output row %d is NULL", o);
+  DeviceGuard g(c->device);
+  if (!g.ok) return fail(c, HRS_EDEVICE, "cannot select HIP device %d", c->device);
+  const hipStream_t hs = static_cast<hipStream_t>(stream);
+  if (ragged_takes_plain(c, all_full))
+    return run_apply(c, c->g.data(), c->p, c->k, in_rows, in_stride, out_rows, out_stride, len, nstripes, hs,
+                     static_encode_family(c));
+  hrs_codec::BatchSlot* slot = nullptr;
+  st = upload(c, valid, nstripes * static_cast<size_t>(c->k) * sizeof(uint32_t), valid, 0, hs, &slot);
+  if (st != HRS_OK) return st;
+  st = run_ragged(c, in_rows, in_stride, out_rows, out_stride, len, nstripes,
+                  reinterpret_cast<const uint32_t*>(slot->dev), hs);
+  slot_used(slot, hs);
+  return st;
 }
 
 hrs_status hrs_decode_dev(hrs_codec* c, const uint8_t* const* rows, size_t in_stride, uint8_t* const* out_rows,

@@ -1,5 +1,6 @@
 // Host-memory batches (hrs_decode_batch_host, hrs_encode_batch_host, the
-// scrub / heal / heal-erased host batches, each with its block-CRC-32 form):
+// scrub / heal / heal-erased host batches, each with its block-CRC-32 form,
+// and the ragged encode hrs_encode_ragged_batch_host):
 // memory classification and the zero-copy knobs, the chunk pipeline (chunks of
 // stripes through a ring of device slots, H2D of exactly the rows read, D2H of
 // exactly the rows written), its three jobs, and the device sets. The repair
@@ -250,6 +251,7 @@ struct HostJob {
   std::function<hrs_status(const Chunk&)> compute;
   std::function<int(size_t)> writes;
   std::function<hrs_status(size_t, size_t, std::vector<DirtyCell>&)> dirty;
+  std::function<size_t(size_t, int)> in_bytes;
 };
 
 hrs_status host_batch(hrs_codec* c, const HostJob& job) {
@@ -257,6 +259,7 @@ hrs_status host_batch(hrs_codec* c, const HostJob& job) {
   uint8_t* const hout = job.hout;
   const size_t len = job.len, nstripes = job.nstripes;
   const bool has_dirty = static_cast<bool>(job.dirty);
+  const bool ragged = static_cast<bool>(job.in_bytes);
   const size_t dpitch = (len + 255) & ~static_cast<size_t>(255);
   const size_t img_stripe = dpitch * static_cast<size_t>(job.img_rows);
   const size_t out_stripe_dev = dpitch * static_cast<size_t>(job.out_rows_max);
@@ -344,9 +347,19 @@ hrs_status host_batch(hrs_codec* c, const HostJob& job) {
     for (size_t i = 0; i < ns; ++i) {
       const uint8_t* src = pinned ? hin + (s0 + i) * job.in_stripe : h.pin + i * img_stripe;
       for (const RowRun& r : job.reads(s0 + i)) {
-        hrs_status st = copy_rows(c, dimg + i * img_stripe + r.l0 * dpitch, src + r.l0 * hrow, hrow, dpitch, len, r.cnt,
-                                  hipMemcpyHostToDevice, s_in);
-        if (st != HRS_OK) return st;
+        if (!ragged) {
+          hrs_status st = copy_rows(c, dimg + i * img_stripe + r.l0 * dpitch, src + r.l0 * hrow, hrow, dpitch, len,
+                                    r.cnt, hipMemcpyHostToDevice, s_in);
+          if (st != HRS_OK) return st;
+          continue;
+        }
+        for (int l = r.l0; l < r.l0 + r.cnt; ++l) {  // cell by cell, its leading bytes only
+          const size_t nb = job.in_bytes(s0 + i, l);
+          if (nb == 0) continue;
+          hrs_status st = copy_rows(c, dimg + i * img_stripe + l * dpitch, src + l * hrow, hrow, dpitch, nb, 1,
+                                    hipMemcpyHostToDevice, s_in);
+          if (st != HRS_OK) return st;
+        }
       }
     }
     if (duplex) {
@@ -390,8 +403,10 @@ hrs_status host_batch(hrs_codec* c, const HostJob& job) {
         for (const RowRun& r : job.reads(s0 + i))
           for (int q = 0; q < r.cnt; ++q) {
             const int l = r.l0 + q;
+            const size_t nb = ragged ? job.in_bytes(s0 + i, l) : len;
+            if (nb == 0) continue;
             jobs.push_back(
-                {h.pin + i * img_stripe + l * dpitch, hin + (s0 + i) * job.in_stripe + l * job.in_row, len, nt});
+                {h.pin + i * img_stripe + l * dpitch, hin + (s0 + i) * job.in_stripe + l * job.in_row, nb, nt});
           }
       pool.run(jobs);
     }
@@ -650,6 +665,70 @@ hrs_status encode_batch_host_entry(hrs_codec* c, uint8_t* stripes, size_t row_st
   return host_batch_call(c, stripes, span, nullptr, 0, HostCrcs{c, nstripes * n, crc_in, crc_out}, true, job);
 }
 
+// hrs_encode_ragged_batch_host: hrs_encode_batch_host over data cells of which
+// only the leading valid[s * k + j] bytes hold data (HOST words; include/hrs.h
+// "ragged encode"). The words go up once through a batch slot, on the one
+// launch's stream (pinned) or on slot 0's with the other slot streams waiting
+// for it (staged); a staged chunk copies in only those bytes of each cell.
+hrs_status encode_ragged_batch_host_entry(hrs_codec* c, uint8_t* stripes, size_t row_stride, size_t stripe_stride,
+                                          size_t len, size_t nstripes, const uint32_t* valid) {
+  if (!c) return HRS_EINVAL;
+  if (!stripes || !valid) return fail(c, HRS_EINVAL, "stripes or valid is NULL");
+  if (nstripes == 0 || len == 0) return HRS_OK;
+  bool all_full = false;
+  const hrs_status ok = ragged_valid_ok(c, valid, len, nstripes, &all_full);
+  if (ok != HRS_OK) return ok;
+  if (ragged_takes_plain(c, all_full))
+    return encode_batch_host_entry(c, stripes, row_stride, stripe_stride, len, nstripes, false, nullptr, nullptr);
+  const int k = c->k, p = c->p;
+  const size_t span = batch_span(nstripes, stripe_stride, c->n, row_stride, len);
+  const size_t valid_bytes = nstripes * static_cast<size_t>(k) * sizeof(uint32_t);
+  auto job = [&](HostCrcs&) -> hrs_status {
+    std::vector<const uint8_t*> in(k);
+    std::vector<uint8_t*> outp(p);
+    hrs_codec::BatchSlot* slot = nullptr;
+    // stripes [s0, s0 + ns) on hs, laid out as for encode_batch_host_entry's encode
+    auto encode = [&](hipStream_t hs, size_t s0, size_t ns, const uint8_t* img, size_t row, size_t img_stride,
+                      uint8_t* par, size_t par_stride) -> hrs_status {
+      for (int i = 0; i < k; ++i) in[i] = img + static_cast<size_t>(p + i) * row;
+      for (int r = 0; r < p; ++r) outp[r] = par + static_cast<size_t>(r) * row;
+      return run_ragged(c, in.data(), img_stride, outp.data(), par_stride, len, ns,
+                        reinterpret_cast<const uint32_t*>(slot->dev) + s0 * static_cast<size_t>(k), hs);
+    };
+    uint8_t* zs = nullptr;
+    if (zero_copy_on() && host_device_ptr(stripes, span, &zs))  // in place, dead windows never cross the link
+      return zero_copy_call(c, [&](hipStream_t hs) {
+        hrs_status st = upload(c, valid, valid_bytes, valid, 0, hs, &slot);
+        if (st != HRS_OK) return st;
+        st = encode(hs, 0, nstripes, zs, row_stride, stripe_stride, zs, stripe_stride);
+        slot_used(slot, hs);
+        return st;
+      });
+    hrs_status st = hbatch_slot(c, 0, 0, 0);
+    if (st != HRS_OK) return st;
+    const hipStream_t first = c->hbatch[0].stream;
+    if ((st = upload(c, valid, valid_bytes, valid, 0, first, &slot)) != HRS_OK) return st;
+    slot_used(slot, first);
+    for (int i = 1; i < hrs::kHostBatchSlots; ++i) {
+      if ((st = hbatch_slot(c, i, 0, 0)) != HRS_OK) return st;
+      const hipError_t e = hipStreamWaitEvent(c->hbatch[i].stream, slot->done, 0);
+      if (e != hipSuccess) return hip_fail(c, e, "hipStreamWaitEvent");
+    }
+    const std::vector<RowRun> data_rows{{p, k}};
+    HostJob hj{stripes, row_stride, stripe_stride, c->n, stripes, row_stride, stripe_stride, p, len, nstripes};
+    hj.reads = [&](size_t) -> const std::vector<RowRun>& { return data_rows; };
+    hj.writes = [&](size_t) { return p; };
+    hj.in_bytes = [&](size_t s, int l) { return static_cast<size_t>(valid[s * static_cast<size_t>(k) + (l - p)]); };
+    hj.compute = [&](const Chunk& q) {
+      return encode(q.hs, q.s0, q.ns, q.img, q.pitch, q.img_stripe, q.out, q.out_stripe);
+    };
+    st = host_batch(c, hj);
+    slot_used(slot, first);  // the table's slot is reused only after this job's kernels
+    return st;
+  };
+  return host_batch_call(c, stripes, span, nullptr, 0, HostCrcs{c, 0, nullptr, nullptr}, true, job);
+}
+
 // hrs_scrub_batch_host: every stripe's n rows are its reads, there are no
 // output rows; the reports accumulate in the handle's device buffer (dense,
 // 4 + n words per stripe) and come back in one copy.
@@ -897,6 +976,11 @@ hrs_status hrs_decode_batch_host_crc(hrs_codec* c, const uint8_t* stripes, size_
 hrs_status hrs_encode_batch_host(hrs_codec* c, uint8_t* stripes, size_t row_stride, size_t stripe_stride, size_t len,
                                  size_t nstripes) {
   return encode_batch_host_entry(c, stripes, row_stride, stripe_stride, len, nstripes, false, nullptr, nullptr);
+}
+
+hrs_status hrs_encode_ragged_batch_host(hrs_codec* c, uint8_t* stripes, size_t row_stride, size_t stripe_stride,
+                                        size_t len, size_t nstripes, const uint32_t* valid) {
+  return encode_ragged_batch_host_entry(c, stripes, row_stride, stripe_stride, len, nstripes, valid);
 }
 
 hrs_status hrs_encode_batch_host_crc(hrs_codec* c, uint8_t* stripes, size_t row_stride, size_t stripe_stride,

@@ -209,6 +209,34 @@ def encode_rows(code, data_rows, parity_rows):
     code._check(_lib.lib().hrs_encode_dev(code._handle(), ins, s_in, outs, s_out, L, S, _stream(data_rows[0])))
 
 
+def _ragged_valid(code, valid, S):
+    """The ragged calls' valid lengths as a C-contiguous host uint32 [S, k] array."""
+    torch = _lib.torch
+    if torch is not None and isinstance(valid, torch.Tensor):
+        valid = valid.cpu().numpy()
+    v = np.ascontiguousarray(np.asarray(valid), dtype=np.uint32)
+    if v.shape != (S, code.stripeSize()):
+        raise ValueError(f"valid must be [S, {code.stripeSize()}]")
+    return v
+
+
+def encode_stripes_ragged(code, stripes, valid):
+    """encode_stripes over data cells of which only the leading valid[s, j]
+    bytes hold data (hrs_encode_ragged_dev): cell j of stripe s (location
+    p + j) counts as those bytes followed by zeros, the buffer
+    RaidUtils.readTillEnd hands encodeBulk, and whatever lies behind them is
+    never used; windows wholly behind them are not read. valid: anything
+    convertible to a uint32 [S, k] array (ReadResult.numRead per stripe); it
+    may be reused as soon as the call returns."""
+    k, p = code.stripeSize(), code.paritySize()
+    ins, s_in, L, S = _stripe_rows(stripes, range(p, p + k), k + p)
+    outs, s_out, _, _ = _stripe_rows(stripes, range(p))
+    v = _ragged_valid(code, valid, S)
+    if L and S:
+        code._check(_lib.lib().hrs_encode_ragged_dev(code._handle(), ins, s_in, outs, s_out, L, S, v.ctypes.data,
+                                                     _stream(stripes)))
+
+
 def _decode_stripes(code, stripes, erased, not_to_read, out, crcs=None):
     n = code.stripeSize() + code.paritySize()
     ntr = set(not_to_read)
@@ -322,6 +350,17 @@ def encode_batch_host(code, stripes):
     """hrs_encode_batch_host: parity rows of every stripe of a HOST batch
     stripes[S, n, L] (hops order) from its data rows, in place."""
     _encode_batch_host(code, (code._handle(),), _lib.lib().hrs_encode_batch_host, stripes)
+
+
+def encode_batch_host_ragged(code, stripes, valid):
+    """hrs_encode_ragged_batch_host: encode_batch_host with encode_stripes_ragged's
+    valid lengths. Pinned stripes are encoded in place and dead windows never
+    cross the host link; of any other memory only the valid bytes of each data
+    cell are copied in."""
+    sp, row_stride, stripe_stride, L, S = _host_batch(code, stripes, writable=True)
+    v = _ragged_valid(code, valid, S)
+    code._check(_lib.lib().hrs_encode_ragged_batch_host(code._handle(), sp, row_stride, stripe_stride, L, S,
+                                                        v.ctypes.data))
 
 
 def decode_batch_host_crc(code, stripes, erased, out, crc_in=None, crc_out=None):
