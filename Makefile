@@ -14,7 +14,7 @@ HDRS     := Makefile include/hrs.h lambdafs_amd/csrc/hrs_device.hpp lambdafs_amd
             lambdafs_amd/csrc/hrs_host.hpp lambdafs_amd/csrc/hrs_locator.hpp lambdafs_amd/csrc/hrs_heal_erased.hpp \
             lambdafs_amd/csrc/hrs_heal_erased_device.hpp \
             lambdafs_amd/csrc/hrs_scrub_device.hpp lambdafs_amd/csrc/hrs_repair.hpp lambdafs_amd/csrc/hrs_repair_rule.hpp \
-            lambdafs_amd/csrc/hrs_ragged.hpp
+            lambdafs_amd/csrc/hrs_ragged.hpp lambdafs_amd/csrc/hrs_ragged_device.hpp
 
 # Host translation units of the C ABI (no kernels): lifecycle + queries,
 # matrices, device dispatch, the CRC-32 service, host-buffer path, repair
@@ -25,7 +25,7 @@ API_OBJ  := $(patsubst %,build/%.o,$(API_SRC))
 JNI      := lambdafs_amd/libhrs_jni.so
 HARNESS  := tests/cpp/codec_harness tests/cpp/crc_model tests/cpp/jni_harness tests/cpp/host_logic tests/cpp/crc_tables \
             tests/cpp/copy_pool_test tests/cpp/scrub_logic tests/cpp/heal_logic tests/cpp/heal_erased_logic \
-            tests/cpp/repair_checked_logic
+            tests/cpp/repair_checked_logic tests/cpp/ragged_crc_model
 
 TOOLS    := tools/host_call_rate tools/host_pipeline_sweep tools/host_copy_probe
 
@@ -57,11 +57,14 @@ build/%.o: lambdafs_amd/csrc/%.hip $(HDRS)
 # K = 12 network otherwise stays a loop of runtime mask tests, 5x slower):
 # lift the pragma-unroll size cap for this file.
 build/hrs_fused.o: HIPFLAGS += -mllvm -pragma-unroll-threshold=1000000
+# The ragged encode + CRC carries the same networks and chains.
+build/hrs_ragged_crc.o ragged_crc_resources: HIPFLAGS += -mllvm -pragma-unroll-threshold=1000000
 
 build/hrs_probe.o: include/hrs_probe.h
 
 # `make scrub_resources`, `make scrub_crc_resources`, `make heal_erased_resources`,
-# `make heal_erased_crc_resources`, `make repair_resources`, `make ragged_resources`:
+# `make heal_erased_crc_resources`, `make repair_resources`, `make ragged_resources`,
+# `make ragged_crc_resources`:
 # the compiler's resource report of every kernel of hrs_<name>.hip (the scrub
 # family carries no scratch). Not .PHONY: a phony target takes no pattern rule.
 %_resources: lambdafs_amd/csrc/hrs_%.hip $(HDRS)
@@ -71,7 +74,7 @@ build/hrs_probe.o: include/hrs_probe.h
 
 KOBJ     := build/hrs_kernels.o build/hrs_runtime.o build/hrs_batch.o build/hrs_crc.o build/hrs_fused.o build/hrs_decode_crc.o \
             build/hrs_batch_crc.o build/hrs_scrub.o build/hrs_scrub_crc.o build/hrs_heal_erased.o \
-            build/hrs_heal_erased_crc.o build/hrs_repair.o build/hrs_ragged.o
+            build/hrs_heal_erased_crc.o build/hrs_repair.o build/hrs_ragged.o build/hrs_ragged_crc.o
 
 $(LIB): $(API_OBJ) $(KOBJ) lambdafs_amd/csrc/libhrs.map
 	$(HIPCC) $(HIPFLAGS) -shared -Wl,--version-script=lambdafs_amd/csrc/libhrs.map -o $@ $(API_OBJ) $(KOBJ) \
@@ -140,6 +143,10 @@ tests/cpp/copy_pool_test: tests/cpp/copy_pool_test.cpp lambdafs_amd/csrc/hrs_hos
 tests/cpp/crc_model: tests/cpp/crc_model.cpp lambdafs_amd/csrc/crc32.hpp
 	g++ -O2 -std=c++17 -Wall -o $@ $< -lz
 
+# CPU model of the ragged encode + CRC kernels' CRC side vs zlib over the zero-filled cell.
+tests/cpp/ragged_crc_model: tests/cpp/ragged_crc_model.cpp lambdafs_amd/csrc/crc32.hpp
+	g++ -O2 -std=c++17 -Wall -o $@ $< -lz
+
 # ---- make asan: the host-side code under AddressSanitizer + UBSan (clang,
 # one runtime for all): libhrs's host logic (hrs_api.cpp, host code only: -Xarch_host),
 # the oracle, the JNI shim, and the CPU drivers of each (host-only handles,
@@ -151,7 +158,8 @@ SAN      := -fsanitize=address,undefined -fno-sanitize-recover=undefined -fno-om
 HSAN     := -Xarch_host -fsanitize=address -Xarch_host -fsanitize=undefined -Xarch_host -fno-sanitize-recover=undefined \
             -Xarch_host -fno-omit-frame-pointer
 ASAN_BIN := $(ASAN_DIR)/host_logic $(ASAN_DIR)/jni_harness $(ASAN_DIR)/codec_harness $(ASAN_DIR)/scrub_logic \
-            $(ASAN_DIR)/heal_logic $(ASAN_DIR)/heal_erased_logic $(ASAN_DIR)/repair_checked_logic
+            $(ASAN_DIR)/heal_logic $(ASAN_DIR)/heal_erased_logic $(ASAN_DIR)/repair_checked_logic \
+            $(ASAN_DIR)/ragged_crc_model
 ASAN_LOG := profiles/r06/asan
 
 ASAN_API := $(patsubst %,$(ASAN_DIR)/%.o,$(API_SRC))
@@ -185,6 +193,10 @@ $(ASAN_DIR)/heal_erased_logic: tests/cpp/heal_erased_logic.cpp $(ASAN_DIR)/libhr
 $(ASAN_DIR)/repair_checked_logic: tests/cpp/repair_checked_logic.cpp $(ASAN_DIR)/libhrs.so
 	$(CLANG)++ $(SAN) -std=c++17 -D__HIP_PLATFORM_AMD__ -Iinclude -I/opt/rocm/include -o $@ $< -L$(ASAN_DIR) -lhrs -lz $(ASAN_RPATH)
 
+$(ASAN_DIR)/ragged_crc_model: tests/cpp/ragged_crc_model.cpp lambdafs_amd/csrc/crc32.hpp
+	@mkdir -p $(ASAN_DIR)
+	$(CLANG)++ $(SAN) -std=c++17 -o $@ $< -lz
+
 $(ASAN_DIR)/jni_harness: tests/cpp/jni_harness.c $(ASAN_DIR)/libhrs_jni.so $(ASAN_DIR)/liboracle.so
 	$(CLANG) $(SAN) -std=c11 -Iinclude -Ioracle -o $@ $< -L$(ASAN_DIR) -lhrs_jni -lhrs -loracle -lz -ldl $(ASAN_RPATH)
 
@@ -201,6 +213,7 @@ asan: $(ASAN_BIN)
 	  $(ASAN_DIR)/heal_logic; \
 	  $(ASAN_DIR)/heal_erased_logic; \
 	  $(ASAN_DIR)/repair_checked_logic; \
+	  $(ASAN_DIR)/ragged_crc_model; \
 	  $(ASAN_DIR)/jni_harness --cpu; \
 	  for kp in "10 4" "12 4" "6 3" "3 2"; do $(ASAN_DIR)/codec_harness --host-only $$kp; done' \
 	  > $(ASAN_LOG)/asan_run.log 2>&1 || { cat $(ASAN_LOG)/asan_run.log; exit 1; }

@@ -506,9 +506,9 @@ hrs_status hrs_encode_batch_host_crc(hrs_codec* codec, uint8_t* stripes, size_t 
  * equals len runs the plain encode itself and hrs_last_kernel names that
  * kernel, so always calling the ragged form costs nothing (kernel modes 2 and
  * 3 keep the ragged kernels even then; hrs_set_kernel_mode).
- * Not covered, by design: the synchronous single-stripe host call and its JNI
- * overload, the CRC forms (the CRC of a zero tail is an advance by Z_len),
- * ragged survivors in the repair calls. */
+ * Not covered, by design: the synchronous single-stripe host call, the JNI
+ * overloads (of the CRC forms below too), ragged survivors in the repair
+ * calls. */
 
 /* hrs_encode_dev's rows and layout plus valid. Asynchronous on stream; valid
  * is copied before the call returns (through the handle's per-call table
@@ -525,6 +525,64 @@ hrs_status hrs_encode_ragged_dev(hrs_codec* codec, const uint8_t* const* in_rows
  * success. Synchronous. */
 hrs_status hrs_encode_ragged_batch_host(hrs_codec* codec, uint8_t* stripes, size_t row_stride, size_t stripe_stride,
                                         size_t len, size_t nstripes, const uint32_t* valid);
+
+/* ---- ragged encode + CRC-32: the block checksums of a file's last stripe ----
+ * Encoder.encodeStripe with computeBlockChecksum checksums every source buffer
+ * over its FULL length, zero fill included (updateChecksums:
+ * checksums[i].update(buffs[i], 0, buffs[0].length)), and every parity buffer
+ * (Encoder.java:408-460). These are the two ragged calls above with those
+ * CRCs from the same pass; their semantics are the product of the ragged
+ * contract and the "batches + CRC-32" rules, nothing new is defined:
+ *   - parity and every untouched byte are exactly what the ragged sibling
+ *     leaves; valid is a HOST uint32_t[nstripes * k] array, free on return;
+ *     bytes at or beyond valid never influence any output, a CRC included;
+ *     data cells are never written;
+ *   - the CRC layout is hrs_encode_crc_dev's: crc_out[s * (k + p) + r] is data
+ *     row r for r < k and parity row r - k otherwise, continued from crc_in
+ *     (NULL = fresh); a data row's value is the zlib CRC-32 of its valid bytes
+ *     followed by len - valid zeros, the buffer readTillEnd hands
+ *     updateChecksums;
+ *   - crc_out may be crc_in itself; any other overlap is HRS_EINVAL.
+ * Argument rules, in this order: a NULL handle is HRS_EINVAL with no message;
+ * a NULL pointer argument (valid, crc_out, the row arrays, the stripes) is
+ * HRS_EINVAL; len == 0 or nstripes == 0 returns HRS_OK and touches nothing,
+ * the CRC arrays included; len > UINT32_MAX, a valid entry > len (the stripe
+ * and row named) or a NULL row pointer is HRS_EINVAL; then the overlap rule of
+ * the CRC arrays; only then the device is selected (HRS_EDEVICE for a
+ * host-only handle). Argument errors come before any byte is copied.
+ * Kernels: the shapes hrs_encode_crc_dev fuses (rs (3,2), (6,3), (10,4),
+ * (12,4) and nrs (10,4), (6,3), len a multiple of 2 KiB, 16-byte aligned rows
+ * and strides, kernel mode 0 or 3) take encode_ragged_crc_kernel: a dead 2 KiB
+ * sub-window of a data row costs no load and no table lookup, the one that
+ * holds the boundary is masked before the CRC sees it. Anything else runs the
+ * ragged encode, then crc_ragged_window_kernel over the k + p rows (which
+ * loads no byte at or beyond valid) and the fold, with identical results;
+ * hrs_last_kernel then names the ragged encode's kernel. A batch whose every
+ * entry equals len runs hrs_encode_crc_dev's route in kernel modes 0 and 1 and
+ * hrs_last_kernel names that kernel, so always calling this form costs the
+ * scan of valid; mode 3 keeps the ragged fused kernel for its shapes even
+ * then, mode 2 forces the byte-granular route, modes 1 and 2 never fuse.
+ * HRS_RAGGED_CRC_SUBS = 1 | 2 | 4 | 8 | 16 (read per call; ignored when len is
+ * not a multiple of that many 2 KiB sub-windows) overrides the fused kernel's
+ * window size, for tests and A/B runs.
+ * Not covered, by design: the synchronous single-stripe host call, the JNI
+ * overload, ragged survivors in the repair calls. */
+
+/* hrs_encode_ragged_dev + the CRC-32 of all k + p cells of every stripe.
+ * crc_in / crc_out: DEVICE uint32 [nstripes * (k + p)]. Asynchronous on
+ * stream; valid is copied before the call returns. */
+hrs_status hrs_encode_ragged_crc_dev(hrs_codec* codec, const uint8_t* const* in_rows, size_t in_stride,
+                                     uint8_t* const* out_rows, size_t out_stride, size_t len, size_t nstripes,
+                                     const uint32_t* valid, const uint32_t* crc_in, uint32_t* crc_out, void* stream);
+
+/* hrs_encode_ragged_batch_host + the same CRCs; crc_in / crc_out are HOST
+ * uint32 [nstripes * (k + p)] (read before the first chunk, written once after
+ * the last). Runtime-pinned stripes run as one zero-copy launch in place: dead
+ * windows never cross the host link. hrs_last_host_path as for the sibling,
+ * set only on success. Synchronous. */
+hrs_status hrs_encode_ragged_batch_host_crc(hrs_codec* codec, uint8_t* stripes, size_t row_stride, size_t stripe_stride,
+                                            size_t len, size_t nstripes, const uint32_t* valid,
+                                            const uint32_t* crc_in, uint32_t* crc_out);
 
 /* ---- stripe scrubbing: ReedSolomonCode.computeErrorLocations in bulk ----
  * Whether a stripe at rest is still a codeword, and which cells went bad when
@@ -905,7 +963,12 @@ hrs_status hrs_repair_checked_host(const hrs_codec* codec, uint8_t* const* rows,
  * len to the plain encode (which then follows its own mode) and any other
  * batch to the ragged kernels, vector where the shape has one; 2 forces
  * encode_ragged_bytewise_kernel for every batch; 3 keeps the ragged kernels
- * for an all-full batch too (tests and benchmarks). */
+ * for an all-full batch too (tests and benchmarks).
+ * The ragged encode + CRC calls: 0 and 1 send an all-full batch to
+ * hrs_encode_crc_dev's route (which then follows its own mode); for any other
+ * batch 0 and 3 take encode_ragged_crc_kernel where the shape has one, 1 and 2
+ * never fuse (ragged encode, crc_ragged_window_kernel, fold), 2 with the
+ * byte-granular encode; 3 keeps the ragged kernels for an all-full batch too. */
 hrs_status hrs_set_kernel_mode(hrs_codec* codec, int mode);
 
 #ifdef __cplusplus

@@ -241,6 +241,24 @@ class HipCode : public ErasureCode {
     check(hrs_encode_ragged_batch_host(h_, stripes, rowStride, stripeStride, len, nstripes, valid), h_);
   }
 
+  // The ragged encode with the block CRC-32s of all k + p cells from the same
+  // pass (hrs_encode_ragged_crc_dev: DEVICE crc arrays;
+  // hrs_encode_ragged_batch_host_crc: HOST ones), a data cell's over its valid
+  // bytes followed by zeros; crcIn NULL = fresh, crcOut may be crcIn.
+  void encodeRaggedCrcDev(const uint8_t* const* inRows, size_t inStride, uint8_t* const* outRows, size_t outStride,
+                          size_t len, size_t nstripes, const uint32_t* valid, const uint32_t* crcIn, uint32_t* crcOut,
+                          void* stream) {
+    check(hrs_encode_ragged_crc_dev(h_, inRows, inStride, outRows, outStride, len, nstripes, valid, crcIn, crcOut,
+                                    stream),
+          h_);
+  }
+
+  void encodeRaggedBatchHostCrc(uint8_t* stripes, size_t rowStride, size_t stripeStride, size_t len, size_t nstripes,
+                                const uint32_t* valid, const uint32_t* crcIn, uint32_t* crcOut) {
+    check(hrs_encode_ragged_batch_host_crc(h_, stripes, rowStride, stripeStride, len, nstripes, valid, crcIn, crcOut),
+          h_);
+  }
+
   // RS-specific decodeBulk(readBufs, writeBufs, erasedLocation), ReedSolomonCode.java:168-185.
   void decodeBulk3(const std::vector<uint8_t*>& readBufs, const std::vector<uint8_t*>& writeBufs, size_t len,
                    const std::vector<int>& erased) {

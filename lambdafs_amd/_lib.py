@@ -51,6 +51,7 @@ EXPORTS = (
     "hrs_heal_erased_crc_dev", "hrs_heal_erased_batch_host", "hrs_heal_erased_batch_host_crc",
     "hrs_repair_checked_dev", "hrs_repair_checked_host",
     "hrs_encode_ragged_dev", "hrs_encode_ragged_batch_host",
+    "hrs_encode_ragged_crc_dev", "hrs_encode_ragged_batch_host_crc",
 )
 # include/hrs_probe.h, exported by libhrs_probe.so
 PROBE_EXPORTS = ("hrs_probe_stream", "hrs_probe_rows")
@@ -152,6 +153,8 @@ def lib():
         "hrs_repair_checked_host": ([P, PP, S, P, I, P, P, P, P], I),
         "hrs_encode_ragged_dev": ([P, PP, S, PP, S, S, S, P, P], I),
         "hrs_encode_ragged_batch_host": ([P, P, S, S, S, S, P], I),
+        "hrs_encode_ragged_crc_dev": ([P, PP, S, PP, S, S, S, P, P, P, P], I),
+        "hrs_encode_ragged_batch_host_crc": ([P, P, S, S, S, S, P, P, P], I),
     }
     for name, (args, res) in sigs.items():
         if os.environ.get("HRS_LIB") and not hasattr(L, name):

@@ -297,6 +297,20 @@ hrs_status apply_crc_impl(hrs_codec* c, const uint8_t* m, int nout, int nin, con
 // would read the cells across the link a second time).
 bool encode_crc_one_pass(const hrs_codec* c, size_t len, size_t nstripes);
 bool apply_crc_one_pass(const hrs_codec* c, int nout, int nlive, size_t len);
+// Whether a ragged batch with CRCs takes the plain encode + CRC: every cell
+// full, in kernel modes 0 and 1 (2 keeps the byte-granular ragged route, 3 the
+// ragged fused kernel).
+inline bool ragged_crc_takes_plain(const hrs_codec* c, bool all_full) {
+  return all_full && (c->kernel_mode == 0 || c->kernel_mode == 1);
+}
+// hrs_encode_ragged_crc_dev after its checks, the valid words on the device
+// (dvalid, at the range's first stripe): the one-pass ragged kernel under
+// encode_crc_impl's rule, else run_ragged, the ragged window pass and the
+// fold. raw: crc_raw_bytes_for(len, nstripes, n) under the caller's lease.
+hrs_status encode_ragged_crc_impl(hrs_codec* c, const uint8_t* const* in_rows, size_t in_stride,
+                                  uint8_t* const* out_rows, size_t out_stride, size_t len, size_t nstripes,
+                                  const uint32_t* dvalid, const uint32_t* crc_in, uint32_t* crc_out, hipStream_t s,
+                                  uint32_t* raw);
 
 // ---- stripe scrubbing (hrs_scrub_api.cpp)
 // The code and report_stride checks of the scrub entry points (rs only,

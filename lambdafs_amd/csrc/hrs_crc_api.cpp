@@ -1,8 +1,9 @@
 // The handle's CRC-32 service: the LDS table images, the fold-table cache and
 // its per-stream events, the raw-CRC scratch every device CRC call leases
 // (with_crc_scratch, hrs_codec.hpp), the window pass and the fold, the fused
-// encode + CRC and repair + CRC with their one-pass rules, and the hrs_crc32_dev,
-// hrs_encode_crc_dev and hrs_decode_crc_dev entry points.
+// encode + CRC (plain and ragged) and repair + CRC with their one-pass rules,
+// and the hrs_crc32_dev, hrs_encode_crc_dev, hrs_encode_ragged_crc_dev and
+// hrs_decode_crc_dev entry points.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -15,6 +16,7 @@
 #include "crc32.hpp"
 #include "hrs_crc.hpp"
 #include "hrs_internal.hpp"
+#include "hrs_ragged.hpp"
 
 namespace hrs::api {
 
@@ -353,6 +355,111 @@ hrs_status encode_crc_impl(hrs_codec* c, const uint8_t* const* in_rows, size_t i
   return run_crc(c, rows.data(), strides.data(), n, len, nstripes, crc_in, crc_out, s, raw);
 }
 
+// HRS_RAGGED_CRC_SUBS = 1 | 2 | 4 | 8 | 16: the ragged fused kernel's 2 KiB
+// sub-windows per window instead of fused_subs' choice, so that tests and A/B
+// runs reach the multi-sub-window walk at small sizes. Read per call; ignored
+// when len is not a multiple of that window.
+uint32_t ragged_crc_subs(size_t len, size_t nstripes) {
+  const uint32_t dflt = fused_subs(len, nstripes);
+  const char* e = getenv("HRS_RAGGED_CRC_SUBS");
+  const int x = e ? atoi(e) : 0;
+  if (dflt == 0 || x < 1 || x > 16 || (x & (x - 1)) != 0) return dflt;
+  if (len % (static_cast<size_t>(x) * hrs::kWindowBytes)) return dflt;
+  return static_cast<uint32_t>(x);
+}
+
+// The window pass of the ragged two-pass route: crc_windows over the n rows of
+// every stripe with data row j cut at dvalid[s * k + j] (crc_ragged_window_kernel).
+hrs_status crc_ragged_windows(hrs_codec* c, const uint8_t* const* rows, const size_t* strides, size_t len,
+                              size_t nstripes, const uint32_t* dvalid, hipStream_t s, uint32_t* raw) {
+  hrs_status st = crc_window_tables(c);
+  if (st != HRS_OK) return st;
+  const int n = c->n;
+  bool aligned = true;
+  for (int r = 0; r < n; ++r) aligned &= aligned16(rows[r]) && strides[r] % 16 == 0;
+  for (int r0 = 0; r0 < n; r0 += hrs::kCrcMaxRows) {
+    hrs::RaggedCrcWinArgs a{};
+    a.w.nrows = std::min(hrs::kCrcMaxRows, n - r0);
+    for (int r = 0; r < a.w.nrows; ++r) {
+      a.w.rows[r] = rows[r0 + r];
+      a.w.stride[r] = strides[r0 + r];
+    }
+    a.w.row0 = r0;
+    a.w.nrows_total = n;
+    a.w.len = len;
+    a.w.nwin = len / hrs::kCrcWindow;
+    a.w.tail = len % hrs::kCrcWindow;
+    a.w.nstripes = nstripes;
+    a.w.raw = raw;
+    a.w.tables = c->crc_tables_a;
+    a.valid = dvalid;
+    a.k = c->k;
+    const hipError_t e = hrs::launch_crc_ragged_windows(a, aligned, hrs::device_cu_count(), s);
+    if (e != hipSuccess) return hip_fail(c, e, "ragged crc window launch");
+  }
+  return HRS_OK;
+}
+
+// Ragged encode + CRC-32 of the k sources (each over its valid bytes followed
+// by zeros) and the p parities, hrs_encode_ragged_crc_dev's semantics, with
+// the valid words on the device (dvalid, at the range's first stripe) and raw
+// window CRCs in `raw` (crc_raw_bytes_for(len, nstripes, n)). One pass
+// (encode_ragged_crc_kernel) under encode_crc_impl's rule: kernel mode 0 or 3,
+// a static (k, p) of rs / nrs, whole 2 KiB sub-windows, 16-byte aligned rows
+// and strides. Else run_ragged, then the ragged window pass and the fold, on
+// the same stream, with identical results.
+hrs_status encode_ragged_crc_impl(hrs_codec* c, const uint8_t* const* in_rows, size_t in_stride,
+                                  uint8_t* const* out_rows, size_t out_stride, size_t len, size_t nstripes,
+                                  const uint32_t* dvalid, const uint32_t* crc_in, uint32_t* crc_out, hipStream_t s,
+                                  uint32_t* raw) {
+  const int k = c->k, p = c->p, n = c->n;
+  bool fused = encode_crc_one_pass(c, len, nstripes) && in_stride % 16 == 0 && out_stride % 16 == 0;
+  for (int i = 0; i < k && fused; ++i) fused &= aligned16(in_rows[i]);
+  for (int o = 0; o < p && fused; ++o) fused &= aligned16(out_rows[o]);
+  if (fused) {
+    hrs_status st = crc_window_tables(c);
+    if (st != HRS_OK) return st;
+    const uint32_t subs = ragged_crc_subs(len, nstripes);
+    hrs::EncodeRaggedCrcArgs a{};
+    for (int i = 0; i < k; ++i) a.e.in[i] = in_rows[i];
+    for (int o = 0; o < p; ++o) a.e.out[o] = out_rows[o];
+    a.e.in_stride = in_stride;
+    a.e.out_stride = out_stride;
+    a.e.subs = subs;
+    a.e.rep_mask = crc_rep_mask();
+    a.e.nwin = len / (subs * hrs::kWindowBytes);
+    a.e.nstripes = nstripes;
+    a.e.raw = raw;
+    a.e.tables = c->crc_tables_a;
+    a.valid = dvalid;
+    bool handled = false;
+    const int family = c->kind == HRS_CODE_NRS ? hrs::kStaticCauchy : hrs::kStaticRs;
+    const hipError_t e = hrs::launch_encode_ragged_crc(family, k, p, a, hrs::device_cu_count(), s, &handled);
+    if (e != hipSuccess) return hip_fail(c, e, "ragged encode+crc launch");
+    if (handled) {
+      c->last_kernel = hrs::last_kernel();
+      return crc_fold(c, len, nstripes * n, crc_in, crc_out, s, raw, subs * hrs::kWindowBytes);
+    }
+  }
+  // two passes: the ragged encode (its kernels name the call), then the CRC of
+  // the k sources up to their valid bytes and of the p parities
+  hrs_status st = run_ragged(c, in_rows, in_stride, out_rows, out_stride, len, nstripes, dvalid, s);
+  if (st != HRS_OK) return st;
+  std::vector<const uint8_t*> rows(n);
+  std::vector<size_t> strides(n);
+  for (int i = 0; i < k; ++i) {
+    rows[i] = in_rows[i];
+    strides[i] = in_stride;
+  }
+  for (int o = 0; o < p; ++o) {
+    rows[k + o] = out_rows[o];
+    strides[k + o] = out_stride;
+  }
+  st = crc_ragged_windows(c, rows.data(), strides.data(), len, nstripes, dvalid, s, raw);
+  if (st != HRS_OK) return st;
+  return crc_fold(c, len, nstripes * n, crc_in, crc_out, s, raw, hrs::kCrcWindow);
+}
+
 // out_o = XOR_i m[o][i] * in_i for every stripe, plus the CRC-32 of every
 // output row (crc_out[s * nout + o], continuing crc_in): the Decoder's repair
 // and the checksum of the repaired cells, with raw window CRCs in `raw`
@@ -447,6 +554,37 @@ hrs_status hrs_encode_crc_dev(hrs_codec* c, const uint8_t* const* in_rows, size_
   hipStream_t s = static_cast<hipStream_t>(stream);
   return with_crc_scratch(c, crc_raw_bytes_for(len, nstripes, c->n), s, [&] {
     return encode_crc_impl(c, in_rows, in_stride, out_rows, out_stride, len, nstripes, crc_in, crc_out, s, c->crc_raw);
+  });
+}
+
+hrs_status hrs_encode_ragged_crc_dev(hrs_codec* c, const uint8_t* const* in_rows, size_t in_stride,
+                                     uint8_t* const* out_rows, size_t out_stride, size_t len, size_t nstripes,
+                                     const uint32_t* valid, const uint32_t* crc_in, uint32_t* crc_out, void* stream) {
+  if (!c) return HRS_EINVAL;
+  if (!in_rows || !out_rows || !valid || !crc_out) return fail(c, HRS_EINVAL, "row arrays, valid or crc_out are NULL");
+  if (len == 0 || nstripes == 0) return HRS_OK;
+  bool all_full = false;
+  hrs_status st = ragged_valid_ok(c, valid, len, nstripes, &all_full);
+  if (st != HRS_OK) return st;
+  for (int i = 0; i < c->k; ++i)
+    if (!in_rows[i]) return fail(c, HRS_EINVAL, "input row %d is NULL", i);
+  for (int o = 0; o < c->p; ++o)
+    if (!out_rows[o]) return fail(c, HRS_EINVAL, "output row %d is NULL", o);
+  if ((st = crc_args_ok(c, crc_in, crc_out, nstripes * static_cast<size_t>(c->n))) != HRS_OK) return st;
+  DeviceGuard g(c->device);
+  if (!g.ok) return fail(c, HRS_EDEVICE, "cannot select HIP device %d", c->device);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  return with_crc_scratch(c, crc_raw_bytes_for(len, nstripes, c->n), s, [&]() -> hrs_status {
+    if (ragged_crc_takes_plain(c, all_full))
+      return encode_crc_impl(c, in_rows, in_stride, out_rows, out_stride, len, nstripes, crc_in, crc_out, s,
+                             c->crc_raw);
+    hrs_codec::BatchSlot* slot = nullptr;
+    hrs_status st = upload(c, valid, nstripes * static_cast<size_t>(c->k) * sizeof(uint32_t), valid, 0, s, &slot);
+    if (st != HRS_OK) return st;
+    st = encode_ragged_crc_impl(c, in_rows, in_stride, out_rows, out_stride, len, nstripes,
+                                reinterpret_cast<const uint32_t*>(slot->dev), crc_in, crc_out, s, c->crc_raw);
+    slot_used(slot, s);
+    return st;
   });
 }
 

@@ -1,6 +1,6 @@
 // Host-memory batches (hrs_decode_batch_host, hrs_encode_batch_host, the
 // scrub / heal / heal-erased host batches, each with its block-CRC-32 form,
-// and the ragged encode hrs_encode_ragged_batch_host):
+// and the ragged encodes hrs_encode_ragged_batch_host[_crc]):
 // memory classification and the zero-copy knobs, the chunk pipeline (chunks of
 // stripes through a ring of device slots, H2D of exactly the rows read, D2H of
 // exactly the rows written), its three jobs, and the device sets. The repair
@@ -665,35 +665,49 @@ hrs_status encode_batch_host_entry(hrs_codec* c, uint8_t* stripes, size_t row_st
   return host_batch_call(c, stripes, span, nullptr, 0, HostCrcs{c, nstripes * n, crc_in, crc_out}, true, job);
 }
 
-// hrs_encode_ragged_batch_host: hrs_encode_batch_host over data cells of which
-// only the leading valid[s * k + j] bytes hold data (HOST words; include/hrs.h
-// "ragged encode"). The words go up once through a batch slot, on the one
-// launch's stream (pinned) or on slot 0's with the other slot streams waiting
-// for it (staged); a staged chunk copies in only those bytes of each cell.
+// hrs_encode_ragged_batch_host and hrs_encode_ragged_batch_host_crc (with_crc;
+// HOST arrays of nstripes * n words: encode_ragged_crc_impl instead of
+// run_ragged): hrs_encode_batch_host over data cells of which only the leading
+// valid[s * k + j] bytes hold data (HOST words; include/hrs.h "ragged
+// encode"). The words go up once through a batch slot, on the one launch's
+// stream (pinned) or on slot 0's with the other slot streams waiting for it
+// (staged); a staged chunk copies in only those bytes of each cell, and what
+// the slot image keeps behind them reaches neither parity nor CRC.
 hrs_status encode_ragged_batch_host_entry(hrs_codec* c, uint8_t* stripes, size_t row_stride, size_t stripe_stride,
-                                          size_t len, size_t nstripes, const uint32_t* valid) {
+                                          size_t len, size_t nstripes, const uint32_t* valid, bool with_crc,
+                                          const uint32_t* crc_in, uint32_t* crc_out) {
   if (!c) return HRS_EINVAL;
   if (!stripes || !valid) return fail(c, HRS_EINVAL, "stripes or valid is NULL");
+  if (with_crc && !crc_out) return fail(c, HRS_EINVAL, "crc_out is NULL");
   if (nstripes == 0 || len == 0) return HRS_OK;
   bool all_full = false;
-  const hrs_status ok = ragged_valid_ok(c, valid, len, nstripes, &all_full);
+  hrs_status ok = ragged_valid_ok(c, valid, len, nstripes, &all_full);
   if (ok != HRS_OK) return ok;
-  if (ragged_takes_plain(c, all_full))
-    return encode_batch_host_entry(c, stripes, row_stride, stripe_stride, len, nstripes, false, nullptr, nullptr);
+  const size_t n = static_cast<size_t>(c->n);
+  if (with_crc && (ok = crc_args_ok(c, crc_in, crc_out, nstripes * n)) != HRS_OK) return ok;
+  if (with_crc ? ragged_crc_takes_plain(c, all_full) : ragged_takes_plain(c, all_full))
+    return encode_batch_host_entry(c, stripes, row_stride, stripe_stride, len, nstripes, with_crc, crc_in, crc_out);
   const int k = c->k, p = c->p;
   const size_t span = batch_span(nstripes, stripe_stride, c->n, row_stride, len);
   const size_t valid_bytes = nstripes * static_cast<size_t>(k) * sizeof(uint32_t);
-  auto job = [&](HostCrcs&) -> hrs_status {
+  auto job = [&](HostCrcs& crcs) -> hrs_status {
+    hrs_status st = crcs.on_device();
+    if (st != HRS_OK) return st;
     std::vector<const uint8_t*> in(k);
     std::vector<uint8_t*> outp(p);
     hrs_codec::BatchSlot* slot = nullptr;
-    // stripes [s0, s0 + ns) on hs, laid out as for encode_batch_host_entry's encode
+    // stripes [s0, s0 + ns) on hs, laid out as for encode_batch_host_entry's
+    // encode, with the chunk's slice of the valid words and of the CRC arrays
     auto encode = [&](hipStream_t hs, size_t s0, size_t ns, const uint8_t* img, size_t row, size_t img_stride,
                       uint8_t* par, size_t par_stride) -> hrs_status {
       for (int i = 0; i < k; ++i) in[i] = img + static_cast<size_t>(p + i) * row;
       for (int r = 0; r < p; ++r) outp[r] = par + static_cast<size_t>(r) * row;
-      return run_ragged(c, in.data(), img_stride, outp.data(), par_stride, len, ns,
-                        reinterpret_cast<const uint32_t*>(slot->dev) + s0 * static_cast<size_t>(k), hs);
+      const uint32_t* dvalid = reinterpret_cast<const uint32_t*>(slot->dev) + s0 * static_cast<size_t>(k);
+      if (!crcs) return run_ragged(c, in.data(), img_stride, outp.data(), par_stride, len, ns, dvalid, hs);
+      return with_crc_scratch(c, crc_raw_bytes_for(len, ns, c->n), hs, [&] {
+        return encode_ragged_crc_impl(c, in.data(), img_stride, outp.data(), par_stride, len, ns, dvalid,
+                                      crcs.in(s0 * n), crcs.out(s0 * n), hs, c->crc_raw);
+      });
     };
     uint8_t* zs = nullptr;
     if (zero_copy_on() && host_device_ptr(stripes, span, &zs))  // in place, dead windows never cross the link
@@ -704,8 +718,7 @@ hrs_status encode_ragged_batch_host_entry(hrs_codec* c, uint8_t* stripes, size_t
         slot_used(slot, hs);
         return st;
       });
-    hrs_status st = hbatch_slot(c, 0, 0, 0);
-    if (st != HRS_OK) return st;
+    if ((st = hbatch_slot(c, 0, 0, 0)) != HRS_OK) return st;
     const hipStream_t first = c->hbatch[0].stream;
     if ((st = upload(c, valid, valid_bytes, valid, 0, first, &slot)) != HRS_OK) return st;
     slot_used(slot, first);
@@ -726,7 +739,8 @@ hrs_status encode_ragged_batch_host_entry(hrs_codec* c, uint8_t* stripes, size_t
     slot_used(slot, first);  // the table's slot is reused only after this job's kernels
     return st;
   };
-  return host_batch_call(c, stripes, span, nullptr, 0, HostCrcs{c, 0, nullptr, nullptr}, true, job);
+  const HostCrcs crcs{c, nstripes * n, crc_in, with_crc ? crc_out : nullptr};
+  return host_batch_call(c, stripes, span, nullptr, 0, crcs, true, job);
 }
 
 // hrs_scrub_batch_host: every stripe's n rows are its reads, there are no
@@ -980,7 +994,15 @@ hrs_status hrs_encode_batch_host(hrs_codec* c, uint8_t* stripes, size_t row_stri
 
 hrs_status hrs_encode_ragged_batch_host(hrs_codec* c, uint8_t* stripes, size_t row_stride, size_t stripe_stride,
                                         size_t len, size_t nstripes, const uint32_t* valid) {
-  return encode_ragged_batch_host_entry(c, stripes, row_stride, stripe_stride, len, nstripes, valid);
+  return encode_ragged_batch_host_entry(c, stripes, row_stride, stripe_stride, len, nstripes, valid, false, nullptr,
+                                        nullptr);
+}
+
+hrs_status hrs_encode_ragged_batch_host_crc(hrs_codec* c, uint8_t* stripes, size_t row_stride, size_t stripe_stride,
+                                            size_t len, size_t nstripes, const uint32_t* valid,
+                                            const uint32_t* crc_in, uint32_t* crc_out) {
+  return encode_ragged_batch_host_entry(c, stripes, row_stride, stripe_stride, len, nstripes, valid, true, crc_in,
+                                        crc_out);
 }
 
 hrs_status hrs_encode_batch_host_crc(hrs_codec* c, uint8_t* stripes, size_t row_stride, size_t stripe_stride,

@@ -237,6 +237,24 @@ def encode_stripes_ragged(code, stripes, valid):
                                                      _stream(stripes)))
 
 
+def encode_stripes_ragged_crc(code, stripes, valid, crc_in=None):
+    """encode_stripes_ragged plus the CRC-32 of every cell from the same pass
+    (hrs_encode_ragged_crc_dev), as Encoder.encodeStripe keeps them with
+    computeBlockChecksum: an int32 tensor [S, k + p], columns [source 0..k-1,
+    parity 0..p-1]. A source's CRC covers its valid bytes followed by
+    L - valid zeros, the zero-filled buffer updateChecksums sees; nothing at or
+    beyond valid is read. crc_in ([S, k + p] int32) continues running CRCs."""
+    k, p = code.stripeSize(), code.paritySize()
+    ins, s_in, L, S = _stripe_rows(stripes, range(p, p + k), k + p)
+    outs, s_out, _, _ = _stripe_rows(stripes, range(p))
+    v = _ragged_valid(code, valid, S)
+    cin, crc = _dev_crcs((S, k + p), stripes, L, S, crc_in)
+    if L and S:
+        code._check(_lib.lib().hrs_encode_ragged_crc_dev(code._handle(), ins, s_in, outs, s_out, L, S, v.ctypes.data,
+                                                         cin, crc.data_ptr(), _stream(stripes)))
+    return crc
+
+
 def _decode_stripes(code, stripes, erased, not_to_read, out, crcs=None):
     n = code.stripeSize() + code.paritySize()
     ntr = set(not_to_read)
@@ -361,6 +379,20 @@ def encode_batch_host_ragged(code, stripes, valid):
     v = _ragged_valid(code, valid, S)
     code._check(_lib.lib().hrs_encode_ragged_batch_host(code._handle(), sp, row_stride, stripe_stride, L, S,
                                                         v.ctypes.data))
+
+
+def encode_batch_host_ragged_crc(code, stripes, valid, crc_in=None, crc_out=None):
+    """hrs_encode_ragged_batch_host_crc: encode_batch_host_ragged plus the
+    CRC-32 of every cell, computed on the GPU in the same pass: returns a numpy
+    uint32 array [S, k + p] laid out as encode_stripes_ragged_crc's. crc_in
+    continues running CRCs; crc_out: the array to fill and return (it may be
+    crc_in itself) instead of a new one."""
+    sp, row_stride, stripe_stride, L, S = _host_batch(code, stripes, writable=True)
+    v = _ragged_valid(code, valid, S)
+    cin, crc = _host_crcs((S, code.stripeSize() + code.paritySize()), L, crc_in, crc_out)
+    code._check(_lib.lib().hrs_encode_ragged_batch_host_crc(code._handle(), sp, row_stride, stripe_stride, L, S,
+                                                            v.ctypes.data, cin, crc.ctypes.data))
+    return crc
 
 
 def decode_batch_host_crc(code, stripes, erased, out, crc_in=None, crc_out=None):
