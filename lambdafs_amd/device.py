@@ -434,14 +434,16 @@ def encode_batch_host_multi(codes, stripes):
 
 def apply_rows(code, matrix, in_rows, out_rows):
     """out_o = XOR_i matrix[o, i] * in_i over S stripes (matrix: host uint8 [nout, nin]).
-    Used with coding matrices broadcast over RCCL (bench.py --gpus N)."""
+    Used with coding matrices broadcast over RCCL (bench.py --gpus N). An input
+    whose matrix column is all zero is never read and may be passed as None."""
     m = np.ascontiguousarray(np.asarray(matrix, dtype=np.uint8))
     ins, s_in, L, S = _rows(in_rows)
     outs, s_out, L2, S2 = _rows(out_rows)
     if m.shape != (len(out_rows), len(in_rows)) or (L, S) != (L2, S2):
         raise ValueError("shape mismatch")
+    ref = next(v for v in in_rows if v is not None)
     code._check(_lib.lib().hrs_apply_dev(code._handle(), m.ctypes.data, m.shape[0], m.shape[1], ins, s_in, outs,
-                                         s_out, L, S, _stream(in_rows[0])))
+                                         s_out, L, S, _stream(ref)))
 
 
 def crc32_rows(code, row_views, crc_in=None):

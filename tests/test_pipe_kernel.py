@@ -1,14 +1,16 @@
-"""bitsliced_pipe_kernel (hrs_kernels.hip): the software-pipelined runtime
+"""bitsliced_pipe_kernel (hrs_runtime.hip): the software-pipelined runtime
 kernel that serves 1- and 2-output applies of <= 12 inputs (the 1- and
 2-erasure repairs of ReedSolomonCode.decodeBulk, ReedSolomonCode.java:191-211).
 
 GPU only. Each wave holds two register sets and alternates between them, so
 the cases here make the per-wave task count uneven (more tasks than waves,
 not a multiple of the wave count, 1 task for some waves and 4 for others),
-add row tails (len mod 2 KiB, bytewise kernel) and go through the host's
-input chunking (nin > 16: the last chunk runs with accumulate = 1). Checked
-byte for byte against GF(2^8) products from the oracle's multiply
-(GaloisField.java:148-160).
+and add row tails (len mod 2 KiB, bytewise kernel). Two cases have more than
+16 inputs: in kernel mode 0 the dispatch gives those to
+bitsliced_stream_kernel in one launch (no host chunking; the pipelined
+kernel's accumulating chunk runs in mode 1 only, test_gpu_apply_grid.py).
+Every case names the kernel it must have run. Checked byte for byte against
+GF(2^8) products from the oracle's multiply (GaloisField.java:148-160).
 """
 import numpy as np
 import pytest
@@ -31,6 +33,18 @@ def _reference(m, x):
     return ref
 
 
+# the kernel the dispatch gives each (nout, nin) of the cases below in kernel mode 0
+KERNEL = {
+    (1, 10): "bitsliced_pipe_kernel<1, 12>",
+    (1, 12): "bitsliced_pipe_kernel<1, 12>",
+    (2, 12): "bitsliced_pipe_kernel<2, 12>",
+    (1, 5): "bitsliced_pipe_kernel<1, 8>",
+    (2, 3): "bitsliced_pipe_kernel<2, 4>",
+    (1, 20): "bitsliced_stream_kernel<1, 4>",
+    (2, 17): "bitsliced_stream_kernel<2, 4>",
+}
+
+
 @pytest.mark.parametrize(
     "nout,nin,S,L",
     [
@@ -40,8 +54,8 @@ def _reference(m, x):
         (2, 12, 129, 33 * 2048),       # 2 outputs, 4,257 tasks
         (1, 5, 1000, 5 * 2048 + 16),   # NINB 8 instance, 16-byte tail
         (2, 3, 3, 2048),               # fewer tasks than waves
-        (1, 20, 300, 8 * 2048),        # chunked 16 + 4: pipelined chunk accumulates
-        (2, 17, 200, 8 * 2048),        # chunked 16 + 1
+        (1, 20, 300, 8 * 2048),        # > 16 inputs: the streaming kernel, one launch, five groups of 4 rows
+        (2, 17, 200, 8 * 2048),        # > 16 inputs: streamed, one row in the last group
     ],
 )
 def test_pipe_apply_matches_gf_products(nout, nin, S, L):
@@ -53,6 +67,7 @@ def test_pipe_apply_matches_gf_products(nout, nin, S, L):
     x = torch.randint(0, 256, (S, nin, L), dtype=torch.uint8, device="cuda", generator=g)
     y = torch.full((S, nout, L), 0xA5, dtype=torch.uint8, device="cuda")
     device.apply_rows(code, m, [x[:, i] for i in range(nin)], [y[:, o] for o in range(nout)])
+    assert code.lastKernel() == KERNEL[nout, nin]
     torch.cuda.synchronize()
     ref = _reference(m, x.cpu().numpy())
     got = y.cpu().numpy()
