@@ -14,7 +14,7 @@ HDRS     := Makefile include/hrs.h lambdafs_amd/csrc/hrs_device.hpp lambdafs_amd
             lambdafs_amd/csrc/hrs_host.hpp lambdafs_amd/csrc/hrs_locator.hpp lambdafs_amd/csrc/hrs_heal_erased.hpp \
             lambdafs_amd/csrc/hrs_heal_erased_device.hpp \
             lambdafs_amd/csrc/hrs_scrub_device.hpp lambdafs_amd/csrc/hrs_repair.hpp lambdafs_amd/csrc/hrs_repair_rule.hpp \
-            lambdafs_amd/csrc/hrs_ragged.hpp lambdafs_amd/csrc/hrs_ragged_device.hpp
+            lambdafs_amd/csrc/hrs_ragged.hpp lambdafs_amd/csrc/hrs_ragged_device.hpp lambdafs_amd/csrc/hrs_batch_ragged.hpp
 
 # Host translation units of the C ABI (no kernels): lifecycle + queries,
 # matrices, device dispatch, the CRC-32 service, host-buffer path, repair
@@ -64,7 +64,7 @@ build/hrs_probe.o: include/hrs_probe.h
 
 # `make scrub_resources`, `make scrub_crc_resources`, `make heal_erased_resources`,
 # `make heal_erased_crc_resources`, `make repair_resources`, `make ragged_resources`,
-# `make ragged_crc_resources`:
+# `make ragged_crc_resources`, `make ragged_repair_resources` (hrs_batch_ragged.hip):
 # the compiler's resource report of every kernel of hrs_<name>.hip (the scrub
 # family carries no scratch). Not .PHONY: a phony target takes no pattern rule.
 %_resources: lambdafs_amd/csrc/hrs_%.hip $(HDRS)
@@ -72,9 +72,12 @@ build/hrs_probe.o: include/hrs_probe.h
 	$(HIPCC) $(HIPFLAGS) -Rpass-analysis=kernel-resource-usage -c $< -o build/hrs_$*.report.o 2>&1 | \
 	    grep -E 'Function Name|VGPRs:|SGPRs:|ScratchSize|Occupancy|LDS Size'
 
+# The ragged repair's unit is named after the batch it extends.
+ragged_repair_resources: batch_ragged_resources
+
 KOBJ     := build/hrs_kernels.o build/hrs_runtime.o build/hrs_batch.o build/hrs_crc.o build/hrs_fused.o build/hrs_decode_crc.o \
             build/hrs_batch_crc.o build/hrs_scrub.o build/hrs_scrub_crc.o build/hrs_heal_erased.o \
-            build/hrs_heal_erased_crc.o build/hrs_repair.o build/hrs_ragged.o build/hrs_ragged_crc.o
+            build/hrs_heal_erased_crc.o build/hrs_repair.o build/hrs_ragged.o build/hrs_ragged_crc.o build/hrs_batch_ragged.o
 
 $(LIB): $(API_OBJ) $(KOBJ) lambdafs_amd/csrc/libhrs.map
 	$(HIPCC) $(HIPFLAGS) -shared -Wl,--version-script=lambdafs_amd/csrc/libhrs.map -o $@ $(API_OBJ) $(KOBJ) \

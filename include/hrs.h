@@ -507,8 +507,8 @@ hrs_status hrs_encode_batch_host_crc(hrs_codec* codec, uint8_t* stripes, size_t 
  * kernel, so always calling the ragged form costs nothing (kernel modes 2 and
  * 3 keep the ragged kernels even then; hrs_set_kernel_mode).
  * Not covered, by design: the synchronous single-stripe host call, the JNI
- * overloads (of the CRC forms below too), ragged survivors in the repair
- * calls. */
+ * overloads (of the CRC forms below too). Ragged survivors in the repair
+ * calls: "ragged repair" below. */
 
 /* hrs_encode_dev's rows and layout plus valid. Asynchronous on stream; valid
  * is copied before the call returns (through the handle's per-call table
@@ -566,7 +566,7 @@ hrs_status hrs_encode_ragged_batch_host(hrs_codec* codec, uint8_t* stripes, size
  * not a multiple of that many 2 KiB sub-windows) overrides the fused kernel's
  * window size, for tests and A/B runs.
  * Not covered, by design: the synchronous single-stripe host call, the JNI
- * overload, ragged survivors in the repair calls. */
+ * overload. Ragged survivors in the repair calls: "ragged repair" below. */
 
 /* hrs_encode_ragged_dev + the CRC-32 of all k + p cells of every stripe.
  * crc_in / crc_out: DEVICE uint32 [nstripes * (k + p)]. Asynchronous on
@@ -583,6 +583,81 @@ hrs_status hrs_encode_ragged_crc_dev(hrs_codec* codec, const uint8_t* const* in_
 hrs_status hrs_encode_ragged_batch_host_crc(hrs_codec* codec, uint8_t* stripes, size_t row_stride, size_t stripe_stride,
                                             size_t len, size_t nstripes, const uint32_t* valid,
                                             const uint32_t* crc_in, uint32_t* crc_out);
+
+/* ---- ragged repair: per-cell lengths, zero tails never read or written ----
+ * locationsToReadForDecode picks the k highest-index live locations, in hops
+ * order [parity..., data...] the data cells at the end of the stripe: the
+ * cells a file tail leaves empty. The reference reads none of them: survivors
+ * past the end of the file are ZeroInputStreams (StripeReader.java:111-120),
+ * RaidUtils.readTillEnd zero-fills a short read, ParallelStreamReader.
+ * ReadResult.numRead carries the real count (ParallelStreamReader.java:236-249)
+ * to Decoder.java:349-358, and the repaired block is written and checksummed
+ * only up to toWrite = min(bufSize, limit - written), limit being the lost
+ * block's real length (Decoder.java:345-346, :360-369). A ragged repair batch
+ * is hrs_decode_batch_dev / hrs_decode_batch_host (layout, erased, survivor
+ * choice, HRS_ETOOMANY and the code families rs, nrs, xor, src exactly theirs)
+ * plus one number per cell:
+ *   - valid is a HOST array of uint32_t[nstripes * n] in hops order;
+ *   - valid[s * n + l] is the length of cell l of stripe s.
+ * The calls guarantee:
+ *   - a survivor the stripe's plan reads counts as its valid leading bytes
+ *     followed by len - valid zeros; bytes at or beyond valid never influence
+ *     an output, whatever they hold; the storage of the whole cell (len bytes)
+ *     must still be addressable;
+ *   - output t of stripe s, rebuilding location e = erased[s * max_erased + t],
+ *     receives exactly its first valid[s * n + e] bytes, bit-exact with
+ *     decodeBulk (5-arg, as the sibling runs it) over the zero-filled
+ *     survivors; bytes of the output at or beyond that length are not written
+ *     and keep what they held; outputs are never read;
+ *   - entries of locations a stripe neither reads nor lost are ignored, but
+ *     still range-checked;
+ *   - the vector kernel loads no 2 KiB window of a survivor that lies wholly
+ *     at or beyond its valid, loads and masks the one window that holds the
+ *     boundary, and loads nothing at all for a window in which every output of
+ *     the stripe is dead;
+ *   - the staged host path copies in no survivor byte at or beyond valid and
+ *     copies back no output byte at or beyond it (with HRS_ZEROCOPY=0 no such
+ *     byte is sent to or fetched from the device); runtime-pinned batches run
+ *     as one zero-copy launch in place;
+ *   - stripes that lost nothing write nothing; hrs_last_host_path behaves as
+ *     for the sibling and is set only on success.
+ * Argument rules, in this order: a NULL handle is HRS_EINVAL with no message;
+ * the sibling's argument block (stripes, out, max_erased, erased); a NULL valid
+ * is HRS_EINVAL; len == 0, nstripes == 0 or max_erased == 0 returns HRS_OK and
+ * touches nothing; len > UINT32_MAX or a valid entry > len is HRS_EINVAL with
+ * the stripe and location named; the plans are built, with the sibling's
+ * HRS_EINVAL / HRS_ETOOMANY; a pattern that reads more than 32 survivors is
+ * HRS_EINVAL with the stripe named; only then the device is selected
+ * (HRS_EDEVICE for a host-only handle). Argument errors come before any byte is
+ * copied.
+ * Kernels: batches with at most 4 losses and at most 16 survivors read per
+ * stripe, 16-byte aligned bases and all four strides, take
+ * batch_ragged_kernel<NOUT, NINB> over the whole 2 KiB windows (no
+ * instantiation uses scratch); the row tail, every other shape, unaligned layouts and
+ * kernel mode 2 take batch_ragged_bytewise_kernel (hrs_last_kernel names them
+ * by the plain batch's tail rule). A batch whose every entry equals len takes
+ * the plain call's route in kernel modes 0 and 1 and hrs_last_kernel names
+ * that kernel, so always calling the ragged form costs one scan of valid; mode
+ * 3 keeps the ragged kernels even then (hrs_set_kernel_mode).
+ * Not covered, by design: patterns that read more than 32 survivors (codes
+ * with k > 32, which the plain call serves one stripe at a time: HRS_EINVAL
+ * here), the CRC forms of the ragged repair, the JNI overloads and the
+ * single-stripe host call. */
+
+/* hrs_decode_batch_dev's layout plus valid. Asynchronous on stream; valid is
+ * copied before the call returns (in plan order, through the handle's per-call
+ * table slots, with the plans) and may be reused at once. */
+hrs_status hrs_decode_batch_ragged_dev(hrs_codec* codec, const uint8_t* stripes, size_t row_stride,
+                                       size_t stripe_stride, const int* erased, int max_erased, uint8_t* out,
+                                       size_t out_row_stride, size_t out_stripe_stride, size_t len,
+                                       size_t nstripes, const uint32_t* valid, void* stream);
+
+/* hrs_decode_batch_host's layout plus valid (HOST stripes and out).
+ * Synchronous: the outputs' leading bytes are in place when the call returns. */
+hrs_status hrs_decode_batch_ragged_host(hrs_codec* codec, const uint8_t* stripes, size_t row_stride,
+                                        size_t stripe_stride, const int* erased, int max_erased, uint8_t* out,
+                                        size_t out_row_stride, size_t out_stripe_stride, size_t len,
+                                        size_t nstripes, const uint32_t* valid);
 
 /* ---- stripe scrubbing: ReedSolomonCode.computeErrorLocations in bulk ----
  * Whether a stripe at rest is still a codeword, and which cells went bad when
@@ -968,7 +1043,12 @@ hrs_status hrs_repair_checked_host(const hrs_codec* codec, uint8_t* const* rows,
  * hrs_encode_crc_dev's route (which then follows its own mode); for any other
  * batch 0 and 3 take encode_ragged_crc_kernel where the shape has one, 1 and 2
  * never fuse (ragged encode, crc_ragged_window_kernel, fold), 2 with the
- * byte-granular encode; 3 keeps the ragged kernels for an all-full batch too. */
+ * byte-granular encode; 3 keeps the ragged kernels for an all-full batch too.
+ * The ragged repair calls: 0 and 1 send a batch whose every valid entry equals
+ * len to the plain batch's route (which then follows its own mode) and any
+ * other batch to the ragged kernels, batch_ragged_kernel where the shape has
+ * one; 2 forces batch_ragged_bytewise_kernel for every batch; 3 keeps the
+ * ragged kernels for an all-full batch too. */
 hrs_status hrs_set_kernel_mode(hrs_codec* codec, int mode);
 
 #ifdef __cplusplus

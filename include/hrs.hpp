@@ -259,6 +259,26 @@ class HipCode : public ErasureCode {
           h_);
   }
 
+  // The ragged repair (hrs_decode_batch_ragged_dev, hrs_decode_batch_ragged_host;
+  // semantics in include/hrs.h): valid[s * n + l] is the length of cell l of
+  // stripe s (hops order); survivors read as zeros behind it, an output is
+  // written only up to it.
+  void decodeBatchRaggedDev(const uint8_t* stripes, size_t rowStride, size_t stripeStride, const int* erased,
+                            int maxErased, uint8_t* out, size_t outRowStride, size_t outStripeStride, size_t len,
+                            size_t nstripes, const uint32_t* valid, void* stream) {
+    check(hrs_decode_batch_ragged_dev(h_, stripes, rowStride, stripeStride, erased, maxErased, out, outRowStride,
+                                      outStripeStride, len, nstripes, valid, stream),
+          h_);
+  }
+
+  void decodeBatchRaggedHost(const uint8_t* stripes, size_t rowStride, size_t stripeStride, const int* erased,
+                             int maxErased, uint8_t* out, size_t outRowStride, size_t outStripeStride, size_t len,
+                             size_t nstripes, const uint32_t* valid) {
+    check(hrs_decode_batch_ragged_host(h_, stripes, rowStride, stripeStride, erased, maxErased, out, outRowStride,
+                                       outStripeStride, len, nstripes, valid),
+          h_);
+  }
+
   // RS-specific decodeBulk(readBufs, writeBufs, erasedLocation), ReedSolomonCode.java:168-185.
   void decodeBulk3(const std::vector<uint8_t*>& readBufs, const std::vector<uint8_t*>& writeBufs, size_t len,
                    const std::vector<int>& erased) {

@@ -1,6 +1,7 @@
 // Device-resident repair batches: heterogeneous batches (one erasure pattern
 // per stripe, plans uploaded through pinned slots, one batch launch) with
-// their block-CRC-32 form (hrs_decode_batch_dev, hrs_decode_batch_crc_dev),
+// their block-CRC-32 form (hrs_decode_batch_dev, hrs_decode_batch_crc_dev)
+// and their ragged form (hrs_decode_batch_ragged_dev: per-cell lengths),
 // and the per-call table slots every unit uploads through. The host-memory
 // batches that run their chunks through run_batch are in hrs_hostbatch_api.cpp.
 #include <hip/hip_runtime.h>
@@ -11,6 +12,7 @@
 #include <vector>
 
 #include "../../include/hrs.h"
+#include "hrs_batch_ragged.hpp"
 #include "hrs_codec.hpp"
 #include "hrs_crc.hpp"
 #include "hrs_internal.hpp"
@@ -133,8 +135,37 @@ hrs::BatchArgs batch_args(const BatchPlanSet& ps, const BatchGeom& g, size_t s0)
   return a;
 }
 
+// The ragged launches of stripes [s0, s0 + ns): batch_ragged_kernel over the
+// whole 2 KiB windows of an aligned batch of its shapes, the byte-granular
+// kernel over the row tail, every other shape or layout and kernel mode 2.
+hrs_status launch_batch_ragged(hrs_codec* c, const BatchPlanSet& ps, const BatchGeom& g, size_t s0, size_t ns,
+                               hipStream_t hs) {
+  hrs::BatchRaggedArgs a{};
+  a.b = batch_args(ps, g, s0);
+  a.lens = ps.dlens + s0 * static_cast<size_t>(ps.len_words);
+  a.words = ps.len_words;
+  a.nin_words = ps.max_nin;
+  const bool vec = c->kernel_mode != 2 && vector_aligned(g) && hrs::batch_ragged_vector_shape(ps.max_nout, ps.max_nin);
+  a.b.nwin = vec ? g.len / hrs::kWindowBytes : 0;
+  if (a.b.nwin > 0) {
+    a.b.ntasks = a.b.nwin * ns;
+    hipError_t e = hrs::launch_batch_ragged(a, ps.max_nout, ps.max_nin, hs);
+    if (e != hipSuccess) return hip_fail(c, e, "ragged batch launch");
+    c->last_kernel = hrs::last_kernel();
+  }
+  a.b.col0 = a.b.nwin * hrs::kWindowBytes;
+  if (a.b.col0 < g.len) {
+    a.b.ntasks = (g.len - a.b.col0) * ns;
+    hipError_t e = hrs::launch_batch_ragged_bytewise(a, hs);
+    if (e != hipSuccess) return hip_fail(c, e, "ragged batch bytewise launch");
+    if (a.b.nwin == 0) c->last_kernel = hrs::last_kernel();  // the call's only kernel
+  }
+  return HRS_OK;
+}
+
 hrs_status launch_batch(hrs_codec* c, const BatchPlanSet& ps, const BatchGeom& g, size_t s0, size_t ns,
-                        hipStream_t hs) {
+                        hipStream_t hs, bool ragged = false) {
+  if (ragged) return launch_batch_ragged(c, ps, g, s0, ns, hs);
   if (!ps.fused) {  // shapes beyond the batch kernel (wide codes): one launch per stripe
     std::vector<const uint8_t*> rows(c->n);
     std::vector<uint8_t*> outs(hrs::kMaxOut);
@@ -215,8 +246,8 @@ hrs_status launch_batch_crc(hrs_codec* c, const BatchPlanSet& ps, const BatchGeo
 }  // namespace
 
 hrs_status run_batch(hrs_codec* c, const BatchPlanSet& ps, const BatchGeom& g, size_t s0, size_t ns,
-                     const BatchCrcs* crc, hipStream_t s) {
-  if (!crc) return launch_batch(c, ps, g, s0, ns, s);
+                     const BatchCrcs* crc, hipStream_t s, bool ragged) {
+  if (!crc) return launch_batch(c, ps, g, s0, ns, s, ragged);
   return with_crc_scratch(c, crc_raw_bytes_for(g.len, ns, crc->max_erased), s,
                           [&] { return launch_batch_crc(c, ps, g, s0, ns, *crc, s, c->crc_raw); });
 }
@@ -241,6 +272,21 @@ void slot_used(hrs_codec::BatchSlot* sl, hipStream_t s) {
 
 hrs_status upload_plans(hrs_codec* c, BatchPlanSet& ps, hipStream_t s) {
   const size_t plan_bytes = ps.plans.size() * sizeof(hrs::BatchPlan);
+  if (!ps.lens.empty()) {  // a ragged batch: the length table behind the pattern indices, same upload
+    const size_t pat_bytes = ps.pat.size() * sizeof(int32_t), len_bytes = ps.lens.size() * sizeof(uint32_t);
+    const hrs_status st = batch_slot_acquire(c, plan_bytes + pat_bytes + len_bytes, &ps.slot);
+    if (st != HRS_OK) return st;
+    std::memcpy(ps.slot->host, ps.plans.data(), plan_bytes);
+    std::memcpy(ps.slot->host + plan_bytes, ps.pat.data(), pat_bytes);
+    std::memcpy(ps.slot->host + plan_bytes + pat_bytes, ps.lens.data(), len_bytes);
+    const hipError_t e =
+        hipMemcpyAsync(ps.slot->dev, ps.slot->host, plan_bytes + pat_bytes + len_bytes, hipMemcpyHostToDevice, s);
+    if (e != hipSuccess) return hip_fail(c, e, "hipMemcpyAsync table");
+    ps.dplans = reinterpret_cast<const hrs::BatchPlan*>(ps.slot->dev);
+    ps.dpat = reinterpret_cast<const int32_t*>(ps.slot->dev + plan_bytes);
+    ps.dlens = reinterpret_cast<const uint32_t*>(ps.slot->dev + plan_bytes + pat_bytes);
+    return HRS_OK;
+  }
   const hrs_status st = upload(c, ps.plans.data(), plan_bytes, ps.pat.data(), ps.pat.size() * sizeof(int32_t), s,
                                &ps.slot);
   if (st != HRS_OK) return st;
@@ -277,6 +323,44 @@ hrs_status decode_batch_args_ok(hrs_codec* c, const BatchGeom& g, const int* era
   return HRS_OK;
 }
 
+hrs_status ragged_batch_args_ok(hrs_codec* c, const BatchGeom& g, const int* erased, int max_erased, size_t nstripes,
+                                const uint32_t* valid, BatchPlanSet& ps, bool* empty, bool* all_full) {
+  *all_full = false;
+  hrs_status st = decode_batch_args_ok(c, g, erased, max_erased, nstripes, 0u, nullptr, nullptr, empty);
+  if (st != HRS_OK) return st;
+  if (!valid) return fail(c, HRS_EINVAL, "valid is NULL");
+  if (*empty) return HRS_OK;
+  if (g.len > UINT32_MAX) return fail(c, HRS_EINVAL, "ragged repair: len %zu exceeds 2^32 - 1", g.len);
+  const size_t n = static_cast<size_t>(c->n);
+  bool full = true;
+  for (size_t s = 0; s < nstripes; ++s)
+    for (size_t l = 0; l < n; ++l) {
+      const uint32_t v = valid[s * n + l];
+      if (v > g.len) return fail(c, HRS_EINVAL, "stripe %zu location %zu: valid %u exceeds len %zu", s, l, v, g.len);
+      full &= v == g.len;
+    }
+  *all_full = full;
+  if ((st = build_batch_plans(c, erased, max_erased, nstripes, ps)) != HRS_OK) return st;
+  for (size_t s = 0; s < nstripes && !ps.fused; ++s)
+    if (ps.plans[ps.pat[s]].nin > hrs::kBatchMaxIn)
+      return fail(c, HRS_EINVAL, "stripe %zu: its pattern reads %d survivors, a ragged repair batch at most %d", s,
+                  ps.plans[ps.pat[s]].nin, hrs::kBatchMaxIn);
+  return HRS_OK;
+}
+
+void plan_order_lengths(const hrs_codec* c, const int* erased, int max_erased, size_t nstripes, const uint32_t* valid,
+                        BatchPlanSet& ps) {
+  const size_t n = static_cast<size_t>(c->n), words = static_cast<size_t>(ps.max_nin + ps.max_nout);
+  ps.len_words = static_cast<int>(words);
+  ps.lens.assign(nstripes * words, 0u);
+  for (size_t s = 0; s < nstripes; ++s) {
+    const hrs::BatchPlan& pl = ps.plans[ps.pat[s]];
+    uint32_t* w = ps.lens.data() + s * words;
+    for (int r = 0; r < pl.nin; ++r) w[r] = valid[s * n + pl.loc[r]];
+    for (int t = 0; t < pl.nout; ++t) w[ps.max_nin + t] = valid[s * n + erased[s * max_erased + t]];
+  }
+}
+
 }  // namespace hrs::api
 
 using namespace hrs::api;
@@ -308,9 +392,40 @@ hrs_status decode_batch_dev_entry(hrs_codec* c, const BatchGeom& g, const int* e
   return st;
 }
 
+// hrs_decode_batch_ragged_dev: the sibling's entry with a length per cell.
+// valid is read on the host and leaves in plan order with the plans' upload,
+// so the caller may reuse it when the call returns.
+hrs_status decode_batch_ragged_dev_entry(hrs_codec* c, const BatchGeom& g, const int* erased, int max_erased,
+                                         size_t nstripes, const uint32_t* valid, void* stream) {
+  if (!c) return HRS_EINVAL;
+  BatchPlanSet ps;
+  bool empty = false, all_full = false;
+  hrs_status st = ragged_batch_args_ok(c, g, erased, max_erased, nstripes, valid, ps, &empty, &all_full);
+  if (st != HRS_OK || empty) return st;
+  DeviceGuard guard(c->device);
+  if (!guard.ok) return fail(c, HRS_EDEVICE, "cannot select HIP device %d", c->device);
+  if (ps.max_nout == 0) return HRS_OK;
+  const bool ragged = !ragged_batch_takes_plain(c, all_full);
+  if (ragged) plan_order_lengths(c, erased, max_erased, nstripes, valid, ps);
+  const hipStream_t hs = static_cast<hipStream_t>(stream);
+  if ((st = upload_plans(c, ps, hs)) != HRS_OK) return st;
+  st = run_batch(c, ps, g, 0, nstripes, nullptr, hs, ragged);
+  slot_used(ps.slot, hs);
+  return st;
+}
+
 }  // namespace
 
 extern "C" {
+
+hrs_status hrs_decode_batch_ragged_dev(hrs_codec* c, const uint8_t* stripes, size_t row_stride, size_t stripe_stride,
+                                       const int* erased, int max_erased, uint8_t* out, size_t out_row_stride,
+                                       size_t out_stripe_stride, size_t len, size_t nstripes, const uint32_t* valid,
+                                       void* stream) {
+  return decode_batch_ragged_dev_entry(
+      c, {stripes, row_stride, stripe_stride, out, out_row_stride, out_stripe_stride, len}, erased, max_erased,
+      nstripes, valid, stream);
+}
 
 hrs_status hrs_decode_batch_dev(hrs_codec* c, const uint8_t* stripes, size_t row_stride, size_t stripe_stride,
                                 const int* erased, int max_erased, uint8_t* out, size_t out_row_stride,

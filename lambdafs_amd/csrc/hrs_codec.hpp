@@ -414,12 +414,20 @@ struct BatchPlanSet {
   std::vector<std::vector<uint8_t>> mats;
   bool fused = true;  // every pattern fits one batch_bitsliced launch
   int max_nout = 0, max_nin = 0;
-  // the device copies (upload_plans; pat indexed by the absolute stripe number) and their slot
+  // ragged batches only (plan_order_lengths): every stripe's cell lengths in
+  // the order of its plan, len_words = max_nin + max_nout words per stripe
+  // (hrs_batch_ragged.hpp); empty for a plain batch
+  std::vector<uint32_t> lens;
+  int len_words = 0;
+  // the device copies (upload_plans; pat and lens indexed by the absolute stripe number) and their slot
   const hrs::BatchPlan* dplans = nullptr;
   const int32_t* dpat = nullptr;
+  const uint32_t* dlens = nullptr;
   hrs_codec::BatchSlot* slot = nullptr;
 };
 hrs_status build_batch_plans(hrs_codec* c, const int* erased, int max_erased, size_t nstripes, BatchPlanSet& ps);
+// The plans and pattern indices, and ps.lens behind them when it is not empty,
+// in one slot upload.
 hrs_status upload_plans(hrs_codec* c, BatchPlanSet& ps, hipStream_t s);
 // Where a batch lies: stripe i's row l at stripes + i * stripe_stride +
 // l * row_stride, its output t at out + i * out_stripe_stride + t * out_row_stride.
@@ -442,8 +450,10 @@ struct BatchCrcs {
 // crc != NULL: with their CRCs, through the handle's raw-CRC scratch (taken and
 // released on s); the plans must have been uploaded. Without CRCs they must
 // have been when ps.fused (else: one run_apply per stripe).
+// ragged (no CRCs, ps.fused, ps.lens uploaded): the ragged kernels
+// (hrs_batch_ragged.hip) with the stripes' slice of the length table.
 hrs_status run_batch(hrs_codec* c, const BatchPlanSet& ps, const BatchGeom& g, size_t s0, size_t ns,
-                     const BatchCrcs* crc, hipStream_t s);
+                     const BatchCrcs* crc, hipStream_t s, bool ragged = false);
 // The argument rules of the decode-batch entry points, in this order: the
 // handle (NULL: HRS_EINVAL, no message), the argument block, the empty batch
 // (*empty = true: return HRS_OK and touch nothing), nstripes < 2^31 unless
@@ -452,6 +462,26 @@ hrs_status run_batch(hrs_codec* c, const BatchPlanSet& ps, const BatchGeom& g, s
 enum : unsigned { kBatchWithCrc = 1u, kBatchDeviceSet = 2u };
 hrs_status decode_batch_args_ok(hrs_codec* c, const BatchGeom& g, const int* erased, int max_erased, size_t nstripes,
                                 unsigned flags, const uint32_t* crc_in, const uint32_t* crc_out, bool* empty);
+
+// ---- ragged repair batches (hrs_batch_api.cpp; kernels: hrs_batch_ragged.hip)
+// Rules 1-7 of hrs_decode_batch_ragged_dev / _host (include/hrs.h), before the
+// device is selected: the handle, decode_batch_args_ok, valid not NULL, the
+// empty batch (*empty = true: return HRS_OK and touch nothing), len <=
+// UINT32_MAX and every one of the nstripes * n HOST words of `valid` <= len
+// (the stripe and location named), the plans, and no pattern beyond the batch
+// kernels' kBatchMaxIn survivors. *all_full: every word equals len.
+hrs_status ragged_batch_args_ok(hrs_codec* c, const BatchGeom& g, const int* erased, int max_erased, size_t nstripes,
+                                const uint32_t* valid, BatchPlanSet& ps, bool* empty, bool* all_full);
+// Whether a ragged repair batch takes the plain batch's route: every cell
+// full, in kernel modes 0 and 1 (2 and 3 keep the ragged kernels).
+inline bool ragged_batch_takes_plain(const hrs_codec* c, bool all_full) {
+  return all_full && (c->kernel_mode == 0 || c->kernel_mode == 1);
+}
+// Fills ps.lens / ps.len_words from valid[s * n + l] (hops order): per stripe
+// the lengths of its plan's inputs in plan order, then of its outputs; the
+// words a stripe's plan does not use are 0.
+void plan_order_lengths(const hrs_codec* c, const int* erased, int max_erased, size_t nstripes, const uint32_t* valid,
+                        BatchPlanSet& ps);
 
 // ---- shared by the CRC entry points
 // crc_out may be crc_in itself; any other overlap of the two n-word arrays is refused (hrs_batch_api.cpp).

@@ -1,6 +1,7 @@
 // Host-memory batches (hrs_decode_batch_host, hrs_encode_batch_host, the
 // scrub / heal / heal-erased host batches, each with its block-CRC-32 form,
-// and the ragged encodes hrs_encode_ragged_batch_host[_crc]):
+// the ragged encodes hrs_encode_ragged_batch_host[_crc] and the ragged repair
+// hrs_decode_batch_ragged_host):
 // memory classification and the zero-copy knobs, the chunk pipeline (chunks of
 // stripes through a ring of device slots, H2D of exactly the rows read, D2H of
 // exactly the rows written), its three jobs, and the device sets. The repair
@@ -252,6 +253,9 @@ struct HostJob {
   std::function<int(size_t)> writes;
   std::function<hrs_status(size_t, size_t, std::vector<DirtyCell>&)> dirty;
   std::function<size_t(size_t, int)> in_bytes;
+  // (optional; the ragged repair) out_bytes(s, t): the leading bytes of output
+  // t of stripe s that go back to the caller; 0 skips the copy.
+  std::function<size_t(size_t, int)> out_bytes;
 };
 
 hrs_status host_batch(hrs_codec* c, const HostJob& job) {
@@ -260,6 +264,7 @@ hrs_status host_batch(hrs_codec* c, const HostJob& job) {
   const size_t len = job.len, nstripes = job.nstripes;
   const bool has_dirty = static_cast<bool>(job.dirty);
   const bool ragged = static_cast<bool>(job.in_bytes);
+  const bool ragged_out = static_cast<bool>(job.out_bytes);
   const size_t dpitch = (len + 255) & ~static_cast<size_t>(255);
   const size_t img_stripe = dpitch * static_cast<size_t>(job.img_rows);
   const size_t out_stripe_dev = dpitch * static_cast<size_t>(job.out_rows_max);
@@ -309,8 +314,11 @@ hrs_status host_batch(hrs_codec* c, const HostJob& job) {
       const uint8_t* pout = h.pin + chunk * img_stripe;
       for (size_t i = 0; i < pend[sl].ns; ++i) {
         const size_t s = pend[sl].s0 + i;
-        for (int t = 0, nw = job.writes(s); t < nw; ++t)
-          jobs.push_back({hout + s * job.out_stripe + t * job.out_row, pout + i * out_stripe_dev + t * dpitch, len});
+        for (int t = 0, nw = job.writes(s); t < nw; ++t) {
+          const size_t nb = ragged_out ? job.out_bytes(s, t) : len;
+          if (nb == 0) continue;
+          jobs.push_back({hout + s * job.out_stripe + t * job.out_row, pout + i * out_stripe_dev + t * dpitch, nb});
+        }
       }
     }
     if (has_dirty) {
@@ -377,9 +385,20 @@ hrs_status host_batch(hrs_codec* c, const HostJob& job) {
     for (size_t i = 0; i < ns; ++i) {
       const size_t s = s0 + i;
       uint8_t* dst = pinned ? hout + s * job.out_stripe : h.pin + chunk * img_stripe + i * out_stripe_dev;
-      st = copy_rows(c, dst, dout + i * out_stripe_dev, pinned ? job.out_row : dpitch, dpitch, len, job.writes(s),
-                     hipMemcpyDeviceToHost, s_out);
-      if (st != HRS_OK) return st;
+      const size_t hrow_out = pinned ? job.out_row : dpitch;
+      if (!ragged_out) {
+        st = copy_rows(c, dst, dout + i * out_stripe_dev, hrow_out, dpitch, len, job.writes(s), hipMemcpyDeviceToHost,
+                       s_out);
+        if (st != HRS_OK) return st;
+        continue;
+      }
+      for (int t = 0, nw = job.writes(s); t < nw; ++t) {  // cell by cell, its leading bytes only
+        const size_t nb = job.out_bytes(s, t);
+        if (nb == 0) continue;
+        st = copy_rows(c, dst + t * hrow_out, dout + i * out_stripe_dev + t * dpitch, hrow_out, dpitch, nb, 1,
+                       hipMemcpyDeviceToHost, s_out);
+        if (st != HRS_OK) return st;
+      }
     }
     return HRS_OK;
   };
@@ -520,15 +539,17 @@ hrs_status host_batch_call(hrs_codec* c, const void* stripes, size_t span, const
 // of nstripes * max_erased words). Pinned stripes and outputs: one batch launch
 // whose kernels read the survivors and write the repaired cells across the
 // host link directly (zero copy), the plans going up first on the same stream.
-hrs_status decode_batch_host_entry(hrs_codec* c, const BatchGeom& g, const int* erased, int max_erased,
-                                   size_t nstripes, bool with_crc, const uint32_t* crc_in, uint32_t* crc_out) {
-  bool empty = false;
-  hrs_status st =
-      decode_batch_args_ok(c, g, erased, max_erased, nstripes, with_crc ? kBatchWithCrc : 0u, crc_in, crc_out, &empty);
-  if (st != HRS_OK || empty) return st;
-  BatchPlanSet ps;
-  st = build_batch_plans(c, erased, max_erased, nstripes, ps);
-  if (st != HRS_OK) return st;
+// The batch after its argument rules, its plans built. valid != NULL (no CRCs;
+// hrs_decode_batch_ragged_host): cell l of stripe s holds valid[s * n + l]
+// leading bytes; the length table goes up with the plans, a staged chunk
+// copies in only those bytes of each survivor and copies back only those of
+// each output, and what the slot images keep behind them the ragged kernels
+// neither read into an output nor overwrite.
+hrs_status decode_batch_host_run(hrs_codec* c, const BatchGeom& g, const int* erased, int max_erased, size_t nstripes,
+                                 BatchPlanSet& ps, bool with_crc, const uint32_t* crc_in, uint32_t* crc_out,
+                                 const uint32_t* valid) {
+  const bool ragged = valid != nullptr;
+  const size_t n = static_cast<size_t>(c->n);
   const size_t len = g.len, ncrc = nstripes * static_cast<size_t>(max_erased);
   const size_t span = batch_span(nstripes, g.stripe_stride, c->n, g.row_stride, len);
   const size_t out_span = batch_span(nstripes, g.out_stripe_stride, max_erased, g.out_row_stride, len);
@@ -543,7 +564,7 @@ hrs_status decode_batch_host_entry(hrs_codec* c, const BatchGeom& g, const int* 
     // stripes [s0, s0 + ns) at `at` on hs, with their CRCs when asked
     auto repair = [&](const BatchGeom& at, size_t s0, size_t ns, hipStream_t hs) {
       const BatchCrcs bc{max_erased, crcs.in(s0 * max_erased), crcs.out(s0 * max_erased)};
-      return run_batch(c, ps, at, s0, ns, crcs ? &bc : nullptr, hs);
+      return run_batch(c, ps, at, s0, ns, crcs ? &bc : nullptr, hs, ragged);
     };
     uint8_t *zs = nullptr, *zo = nullptr;
     if (zero_copy_on() && host_device_ptr(g.stripes, span, &zs) && host_device_ptr(g.out, out_span, &zo))
@@ -592,6 +613,10 @@ hrs_status decode_batch_host_entry(hrs_codec* c, const BatchGeom& g, const int* 
                ps.max_nout, len, nstripes};
     hj.reads = [&](size_t s) -> const std::vector<RowRun>& { return pruns[ps.pat[s]]; };
     hj.writes = [&](size_t s) { return ps.plans[ps.pat[s]].nout; };
+    if (ragged) {
+      hj.in_bytes = [&](size_t s, int l) { return static_cast<size_t>(valid[s * n + l]); };
+      hj.out_bytes = [&](size_t s, int t) { return static_cast<size_t>(valid[s * n + erased[s * max_erased + t]]); };
+    }
     hj.compute = [&](const Chunk& k) {
       return repair({k.img, k.pitch, k.img_stripe, k.out, k.pitch, k.out_stripe, len}, k.s0, k.ns, k.hs);
     };
@@ -601,6 +626,33 @@ hrs_status decode_batch_host_entry(hrs_codec* c, const BatchGeom& g, const int* 
   };
   return host_batch_call(c, g.stripes, span, g.out, out_span, HostCrcs{c, ncrc, crc_in, crc_out},
                          ps.max_nout > 0 || with_crc, job);
+}
+
+hrs_status decode_batch_host_entry(hrs_codec* c, const BatchGeom& g, const int* erased, int max_erased,
+                                   size_t nstripes, bool with_crc, const uint32_t* crc_in, uint32_t* crc_out) {
+  bool empty = false;
+  hrs_status st =
+      decode_batch_args_ok(c, g, erased, max_erased, nstripes, with_crc ? kBatchWithCrc : 0u, crc_in, crc_out, &empty);
+  if (st != HRS_OK || empty) return st;
+  BatchPlanSet ps;
+  st = build_batch_plans(c, erased, max_erased, nstripes, ps);
+  if (st != HRS_OK) return st;
+  return decode_batch_host_run(c, g, erased, max_erased, nstripes, ps, with_crc, crc_in, crc_out, nullptr);
+}
+
+// hrs_decode_batch_ragged_host: rules 1-7, then the sibling's job with the
+// lengths; an all-full batch in kernel modes 0 and 1 is the sibling's job.
+hrs_status decode_batch_ragged_host_entry(hrs_codec* c, const BatchGeom& g, const int* erased, int max_erased,
+                                          size_t nstripes, const uint32_t* valid) {
+  if (!c) return HRS_EINVAL;
+  BatchPlanSet ps;
+  bool empty = false, all_full = false;
+  const hrs_status st = ragged_batch_args_ok(c, g, erased, max_erased, nstripes, valid, ps, &empty, &all_full);
+  if (st != HRS_OK || empty) return st;
+  const bool ragged = ps.max_nout > 0 && !ragged_batch_takes_plain(c, all_full);
+  if (ragged) plan_order_lengths(c, erased, max_erased, nstripes, valid, ps);
+  return decode_batch_host_run(c, g, erased, max_erased, nstripes, ps, false, nullptr, nullptr,
+                               ragged ? valid : nullptr);
 }
 
 // The argument rules of the encode batches, in this order: the handle (NULL:
@@ -985,6 +1037,14 @@ hrs_status hrs_decode_batch_host_crc(hrs_codec* c, const uint8_t* stripes, size_
                                      uint32_t* crc_out) {
   return decode_batch_host_entry(c, {stripes, row_stride, stripe_stride, out, out_row_stride, out_stripe_stride, len},
                                  erased, max_erased, nstripes, true, crc_in, crc_out);
+}
+
+hrs_status hrs_decode_batch_ragged_host(hrs_codec* c, const uint8_t* stripes, size_t row_stride, size_t stripe_stride,
+                                        const int* erased, int max_erased, uint8_t* out, size_t out_row_stride,
+                                        size_t out_stripe_stride, size_t len, size_t nstripes, const uint32_t* valid) {
+  return decode_batch_ragged_host_entry(
+      c, {stripes, row_stride, stripe_stride, out, out_row_stride, out_stripe_stride, len}, erased, max_erased,
+      nstripes, valid);
 }
 
 hrs_status hrs_encode_batch_host(hrs_codec* c, uint8_t* stripes, size_t row_stride, size_t stripe_stride, size_t len,

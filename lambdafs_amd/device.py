@@ -209,14 +209,16 @@ def encode_rows(code, data_rows, parity_rows):
     code._check(_lib.lib().hrs_encode_dev(code._handle(), ins, s_in, outs, s_out, L, S, _stream(data_rows[0])))
 
 
-def _ragged_valid(code, valid, S):
-    """The ragged calls' valid lengths as a C-contiguous host uint32 [S, k] array."""
+def _ragged_valid(code, valid, S, cells=None):
+    """The ragged calls' valid lengths as a C-contiguous host uint32 [S, cells]
+    array (cells: k, the encodes' data cells, unless given)."""
+    cells = code.stripeSize() if cells is None else cells
     torch = _lib.torch
     if torch is not None and isinstance(valid, torch.Tensor):
         valid = valid.cpu().numpy()
     v = np.ascontiguousarray(np.asarray(valid), dtype=np.uint32)
-    if v.shape != (S, code.stripeSize()):
-        raise ValueError(f"valid must be [S, {code.stripeSize()}]")
+    if v.shape != (S, cells):
+        raise ValueError(f"valid must be [S, {cells}]")
     return v
 
 
@@ -289,14 +291,20 @@ def decode_stripes_crc(code, stripes, erased, not_to_read, out, crc_in=None):
     return _decode_stripes(code, stripes, erased, not_to_read, out, (crc_in,))
 
 
-def _decode_batch(code, stripes, erased, out, crcs=None):
-    _, _, L, S = _stripe_rows(stripes, None, code.stripeSize() + code.paritySize())
+def _decode_batch(code, stripes, erased, out, crcs=None, valid=None):
+    n = code.stripeSize() + code.paritySize()
+    _, _, L, S = _stripe_rows(stripes, None, n)
     e = _decode_erased(erased, S)
     if (out.dim() != 3 or tuple(out.shape) != (S, e.shape[1], L) or out.stride(2) != 1
             or out.dtype != _lib.torch.uint8 or out.device != stripes.device):
         raise ValueError("out must be [S, E, L] on the stripes' device")
     args = (code._handle(), stripes.data_ptr(), stripes.stride(1), stripes.stride(0), e.ctypes.data, e.shape[1],
             out.data_ptr(), out.stride(1), out.stride(0), L, S)
+    if valid is not None:
+        v = _ragged_valid(code, valid, S, n)
+        if L and S:
+            code._check(_lib.lib().hrs_decode_batch_ragged_dev(*args, v.ctypes.data, _stream(stripes)))
+        return None
     if crcs is None:
         if L and S:
             code._check(_lib.lib().hrs_decode_batch_dev(*args, _stream(stripes)))
@@ -327,15 +335,30 @@ def decode_batch_crc(code, stripes, erased, out, crc_in=None, crc_out=None):
     return _decode_batch(code, stripes, erased, out, (crc_in, crc_out))
 
 
+def decode_batch_ragged(code, stripes, erased, out, valid):
+    """decode_batch over cells of which only the leading valid[s, l] bytes hold
+    data (hrs_decode_batch_ragged_dev): a survivor counts as those bytes
+    followed by zeros, the buffer RaidUtils.readTillEnd hands decodeBulk, and
+    nothing behind them is read; output t of stripe s receives exactly the
+    first valid[s, erased[s, t]] bytes of the rebuilt cell and keeps the rest
+    of out[s, t] as it was. valid: anything convertible to a uint32 [S, n]
+    array in hops order; it may be reused as soon as the call returns."""
+    _decode_batch(code, stripes, erased, out, valid=valid)
+
+
 # ---- encode and decode over host batches
 
-def _decode_batch_host(code, head, call, stripes, erased, out, crcs=None):
+def _decode_batch_host(code, head, call, stripes, erased, out, crcs=None, valid=None):
     """The library's `call` over a host batch; `head` is its leading handle
     argument, or a device set's handle array and count with `code` its first
-    codec."""
+    codec. valid: the ragged call's lengths, its last argument."""
     sp, row_stride, stripe_stride, L, S = _host_batch(code, stripes)
     e = _decode_erased(erased, S)
     args = (*head, sp, row_stride, stripe_stride, e.ctypes.data, e.shape[1], *_host_out(out, S, e.shape[1], L), L, S)
+    if valid is not None:
+        v = _ragged_valid(code, valid, S, code.stripeSize() + code.paritySize())
+        code._check(call(*args, v.ctypes.data))
+        return None
     if crcs is None:
         code._check(call(*args))
         return None
@@ -362,6 +385,16 @@ def decode_batch_host(code, stripes, erased, out):
     directly). Only each stripe's survivors go over PCIe, only the repaired
     cells come back; chunks of stripes pipeline through the device."""
     _decode_batch_host(code, (code._handle(),), _lib.lib().hrs_decode_batch_host, stripes, erased, out)
+
+
+def decode_batch_host_ragged(code, stripes, erased, out, valid):
+    """hrs_decode_batch_ragged_host: decode_batch_host with decode_batch_ragged's
+    valid lengths ([S, n], hops order). Pinned batches are repaired in place and
+    dead windows never cross the host link; of any other memory only the valid
+    bytes of each survivor are copied in and only the valid bytes of each
+    repaired cell are copied back."""
+    _decode_batch_host(code, (code._handle(),), _lib.lib().hrs_decode_batch_ragged_host, stripes, erased, out,
+                       valid=valid)
 
 
 def encode_batch_host(code, stripes):
