@@ -14,7 +14,8 @@ HDRS     := Makefile include/hrs.h lambdafs_amd/csrc/hrs_device.hpp lambdafs_amd
             lambdafs_amd/csrc/hrs_host.hpp lambdafs_amd/csrc/hrs_locator.hpp lambdafs_amd/csrc/hrs_heal_erased.hpp \
             lambdafs_amd/csrc/hrs_heal_erased_device.hpp \
             lambdafs_amd/csrc/hrs_scrub_device.hpp lambdafs_amd/csrc/hrs_repair.hpp lambdafs_amd/csrc/hrs_repair_rule.hpp \
-            lambdafs_amd/csrc/hrs_ragged.hpp lambdafs_amd/csrc/hrs_ragged_device.hpp lambdafs_amd/csrc/hrs_batch_ragged.hpp
+            lambdafs_amd/csrc/hrs_ragged.hpp lambdafs_amd/csrc/hrs_ragged_device.hpp lambdafs_amd/csrc/hrs_batch_ragged.hpp \
+            lambdafs_amd/csrc/hrs_window_map.hpp
 
 # Host translation units of the C ABI (no kernels): lifecycle + queries,
 # matrices, device dispatch, the CRC-32 service, host-buffer path, repair
@@ -25,7 +26,7 @@ API_OBJ  := $(patsubst %,build/%.o,$(API_SRC))
 JNI      := lambdafs_amd/libhrs_jni.so
 HARNESS  := tests/cpp/codec_harness tests/cpp/crc_model tests/cpp/jni_harness tests/cpp/host_logic tests/cpp/crc_tables \
             tests/cpp/copy_pool_test tests/cpp/scrub_logic tests/cpp/heal_logic tests/cpp/heal_erased_logic \
-            tests/cpp/repair_checked_logic tests/cpp/ragged_crc_model
+            tests/cpp/repair_checked_logic tests/cpp/ragged_crc_model tests/cpp/window_map
 
 TOOLS    := tools/host_call_rate tools/host_pipeline_sweep tools/host_copy_probe
 
@@ -149,6 +150,10 @@ tests/cpp/crc_model: tests/cpp/crc_model.cpp lambdafs_amd/csrc/crc32.hpp
 # CPU model of the ragged encode + CRC kernels' CRC side vs zlib over the zero-filled cell.
 tests/cpp/ragged_crc_model: tests/cpp/ragged_crc_model.cpp lambdafs_amd/csrc/crc32.hpp
 	g++ -O2 -std=c++17 -Wall -o $@ $< -lz
+
+# The window map of the static encode and the runtime-matrix repairs, enumerated (host code only).
+tests/cpp/window_map: tests/cpp/window_map.cpp lambdafs_amd/csrc/hrs_window_map.hpp
+	g++ -O2 -std=c++17 -Wall -o $@ $<
 
 # ---- make asan: the host-side code under AddressSanitizer + UBSan (clang,
 # one runtime for all): libhrs's host logic (hrs_api.cpp, host code only: -Xarch_host),

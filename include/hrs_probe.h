@@ -59,7 +59,13 @@ hrs_status hrs_probe_stream(int op, const void* src, void* dst, size_t bytes, in
  * how the loads are spaced — D rows in flight per wave and M dependent VALU
  * steps per loaded dword in place of the GF math, since HBM serves a
  * spaced-out request stream better than a burst: 0 = all rows' loads first,
- * no math; 1 = D 3, M 12; 2 = D 5, M 6; 3 = D 1, M 0. cell_bytes must be a
+ * no math; 1 = D 3, M 12; 2 = D 5, M 6; 3 = D 1, M 0.
+ * The two 1 KiB halves of a window lie where the coding kernels put them: the
+ * window map of the static encode for the (k, p) mixes (10,4) (6,3) (12,4)
+ * (3,2), of the runtime-matrix repairs for every other mix, under the same
+ * HRS_WINDOW_SPLIT override (a group of windows interleaves its halves H bytes
+ * apart; rows [0, nwrite) still receive the XOR of the same columns).
+ * cell_bytes must be a
  * multiple of 2048 and base of 16 (else HRS_EALIGN); (nread, nwrite) one of
  * (10,4) (10,3) (10,2) (10,1) (10,0) (6,3) (12,4) (12,2) (3,2), with
  * nread + nwrite <= nrows, schedule in [0, 3] (else HRS_EINVAL). Asynchronous

@@ -10,6 +10,7 @@
 #include "gf256.hpp"
 #include "hrs_crc.hpp"
 #include "hrs_internal.hpp"
+#include "hrs_window_map.hpp"
 #include "xor_sched.hpp"
 
 namespace hrs {
@@ -68,23 +69,31 @@ __device__ __forceinline__ void xtime(uint32_t (&p)[8]) {
   p[0] = hi;
 }
 
-// Lane `lane` of the wave owns bytes [lane*16, +16) and [1024 + lane*16, +16)
-// of the 2 KiB window at `p`. Only whole windows reach these kernels; the
+// Lane `lane` of the wave owns bytes [lane*16, +16) and [half + lane*16, +16)
+// of the window at `p`: two coalesced 1 KiB wave accesses `half` bytes apart.
+// half = 1024 is the contiguous 2 KiB window every kernel family but two
+// uses (their results depend on the byte order within a window, or on valid
+// lengths per contiguous window). The plain static encode and the runtime-
+// matrix repairs pass the half distance of their window map (window_pos,
+// hrs_window_map.hpp; wave-uniform, so the second access costs one scalar
+// add): HBM was measured to serve the 10-read / 4-write pattern faster when
+// the pieces a wave stores back to back lie 64 KiB apart (DESIGN.md §3,
+// profiles/window_split/NOTES.md). Only whole windows reach these kernels; the
 // row tail (len % 2 KiB) goes to the byte-granular kernel. Every byte is
 // touched once, so loads and stores are nontemporal (streaming; measured
 // +4% over default-policy accesses, tools/kernel_lab.hip).
-__device__ __forceinline__ void load_row(const uint8_t* p, int lane, uint32_t (&w)[8]) {
+__device__ __forceinline__ void load_row(const uint8_t* p, int lane, uint32_t (&w)[8], uint32_t half = 1024) {
   const u32x4 x = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(p + lane * 16));
-  const u32x4 y = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(p + 1024 + lane * 16));
+  const u32x4 y = __builtin_nontemporal_load(reinterpret_cast<const u32x4*>(p + half + lane * 16));
   w[0] = x[0]; w[1] = x[1]; w[2] = x[2]; w[3] = x[3];
   w[4] = y[0]; w[5] = y[1]; w[6] = y[2]; w[7] = y[3];
 }
 
-__device__ __forceinline__ void store_row(uint8_t* p, int lane, const uint32_t (&w)[8]) {
+__device__ __forceinline__ void store_row(uint8_t* p, int lane, const uint32_t (&w)[8], uint32_t half = 1024) {
   const u32x4 x = {w[0], w[1], w[2], w[3]};
   const u32x4 y = {w[4], w[5], w[6], w[7]};
   __builtin_nontemporal_store(x, reinterpret_cast<u32x4*>(p + lane * 16));
-  __builtin_nontemporal_store(y, reinterpret_cast<u32x4*>(p + 1024 + lane * 16));
+  __builtin_nontemporal_store(y, reinterpret_cast<u32x4*>(p + half + lane * 16));
 }
 
 // Same accesses from a wave-uniform row base plus the lane's 32-bit byte
@@ -163,6 +172,19 @@ __device__ __forceinline__ WaveTasks wave_tasks(uint64_t ntasks, int order) {
   const uint64_t per = (ntasks + gridDim.x - 1) / gridDim.x;
   const uint64_t lo = per * blockIdx.x;
   return {lo + w, lo + per < ntasks ? lo + per : ntasks, 0, 0xFFFFFFFFu, wpb};
+}
+
+// Task t of a launch whose rows hold nwin whole windows: its stripe and where
+// in the row its window lies under the launch's window map (wave-uniform).
+struct TaskPos {
+  uint64_t stripe, off;
+  uint32_t half;
+};
+
+__device__ __forceinline__ TaskPos task_pos(const RowArgs& a, uint64_t t) {
+  const uint64_t stripe = t / a.nwin;
+  const WindowPos wp = window_pos(t - stripe * a.nwin, a.nwin, a.split);
+  return {stripe, wp.off, wp.half};
 }
 
 // mask[o][r][q]: the input bit-planes of data row r that feed bit-plane q of

@@ -18,7 +18,9 @@ constexpr int kMaxOut = 8;
 
 // One wave owns a 2 KiB column window of every row of one stripe: each lane
 // moves 2 x 16 B per row (lane*16 and 1024 + lane*16), so both load
-// instructions of a row are fully coalesced 1 KiB wave accesses.
+// instructions of a row are fully coalesced 1 KiB wave accesses. (The plain
+// static encode and the runtime-matrix kernels place the second 1 KiB further
+// on in the row: hrs_window_map.hpp.)
 constexpr int kWindowBytes = 2048;
 constexpr int kBlockThreads = 256;
 constexpr int kWavesPerBlock = kBlockThreads / 64;
@@ -36,6 +38,8 @@ struct RowArgs {
   int nout;
   int accumulate;                 // 1: XOR into existing outputs (input chunking)
   int order;                      // window -> wave order (hrs_launch.hpp task_order), set at launch
+  int split;                      // window map (hrs_window_map.hpp): log2(half distance / 1 KiB), 0 = contiguous;
+                                  // set at launch by the static encode and the runtime-matrix kernels only
 };
 
 inline void set_coef(RowArgs& a, int o, int i, uint8_t v) {

@@ -50,8 +50,8 @@ __device__ __forceinline__ void encode_static_body(const RowArgs& a) {
   for (uint32_t j = 0; j < 0xFFFFFFFFu; ++j) {
     const uint64_t t = wt.at(j);
     if (t >= wt.end) break;
-    const uint64_t stripe = t / a.nwin;
-    const uint64_t off = (t - stripe * a.nwin) * kWindowBytes;
+    const TaskPos tp = task_pos(a, t);
+    const uint64_t stripe = tp.stripe, off = tp.off;
     uint32_t acc[P][8];
     uint32_t pend[P][8];
     bool has[P][8];  // compile-time after unrolling
@@ -66,7 +66,7 @@ __device__ __forceinline__ void encode_static_body(const RowArgs& a) {
 #pragma unroll
     for (int r = 0; r < K; ++r) {
       uint32_t w[8];
-      load_row(a.in[r] + stripe * a.in_stride + off, lane, w);
+      load_row(a.in[r] + stripe * a.in_stride + off, lane, w, tp.half);
       bitslice(w);
       encode_row_acc<K, P, MATRIX>(r, w, acc, pend, has);
     }
@@ -78,7 +78,7 @@ __device__ __forceinline__ void encode_static_body(const RowArgs& a) {
 #pragma unroll
     for (int o = 0; o < P; ++o) {
       bitslice(acc[o]);
-      store_row(a.out[o] + stripe * a.out_stride + off, lane, acc[o]);
+      store_row(a.out[o] + stripe * a.out_stride + off, lane, acc[o], tp.half);
     }
   }
 }
@@ -174,7 +174,8 @@ hipError_t launch_static(const RowArgs& a, hipStream_t s) {
   auto kern = encode_static_kernel<K, P>;
   note_kernel_t("encode_static_kernel", K, P);
   const unsigned g = stream_grid(a.ntasks);
-  hipLaunchKernelGGL(kern, dim3(g), dim3(kBlockThreads), 0, s, with_order(a, kOrderStaticEncode));
+  hipLaunchKernelGGL(kern, dim3(g), dim3(kBlockThreads), 0, s,
+                     with_split(with_order(a, kOrderStaticEncode), kSplitStaticEncode));
   return hipGetLastError();
 }
 
@@ -183,7 +184,8 @@ hipError_t launch_cauchy(const RowArgs& a, hipStream_t s) {
   auto kern = encode_cauchy_kernel<K, P>;
   note_kernel_t("encode_cauchy_kernel", K, P);
   const unsigned g = stream_grid(a.ntasks);
-  hipLaunchKernelGGL(kern, dim3(g), dim3(kBlockThreads), 0, s, with_order(a, kOrderStaticEncode));
+  hipLaunchKernelGGL(kern, dim3(g), dim3(kBlockThreads), 0, s,
+                     with_split(with_order(a, kOrderStaticEncode), kSplitStaticEncode));
   return hipGetLastError();
 }
 

@@ -10,6 +10,7 @@
 #include <type_traits>
 
 #include "hrs_internal.hpp"
+#include "hrs_window_map.hpp"
 
 namespace hrs {
 
@@ -94,6 +95,36 @@ constexpr int kOrderScrub = 1;         // scrub windows (not swept: the encode's
 template <class A>
 inline A with_order(A a, int dflt) {
   a.order = task_order(dflt);
+  return a;
+}
+
+// Window map of the plain static encode and the runtime-matrix kernels
+// (hrs_window_map.hpp): the half distance in bytes between a wave task's two
+// 1 KiB pieces, 1024 = contiguous windows. Each family passes its measured
+// default (tools/bench_split.py, profiles/window_split/NOTES.md);
+// HRS_WINDOW_SPLIT=<bytes> overrides both families (A/B runs, tests), read per
+// launch like HRS_TASK_ORDER. A value that is not a power of two in
+// [1 KiB, 1 MiB] is ignored. Returns log2(bytes / 1 KiB), the kernels' form.
+inline int window_split(int dflt_bytes) {
+  const char* e = getenv("HRS_WINDOW_SPLIT");
+  if (e && *e) {
+    const int s = split_of_bytes(atoll(e));
+    if (s >= 0) return s;
+  }
+  return split_of_bytes(dflt_bytes);
+}
+
+// Measured (profiles/window_split/): 32 KiB and 64 KiB both run bench.py's
+// RS(10,4) 1 MiB x 1,024 encode 11 % and its 1-loss repair 10 % faster than
+// contiguous windows; 4, 16, 128 and 256 KiB do nothing. 32 KiB also reaches
+// 64 KiB cells (a row shorter than 2H has no strided group) and lost on no
+// shape swept, so both families take it without a row-length rule.
+constexpr int kSplitStaticEncode = 32768;  // encode_static / encode_cauchy
+constexpr int kSplitRuntime = 32768;       // bitsliced (plain, pipelined, streaming) repairs
+
+template <class A>
+inline A with_split(A a, int dflt_bytes) {
+  a.split = window_split(dflt_bytes);
   return a;
 }
 

@@ -10,8 +10,9 @@
 //     (hrs_probe_rows): 2 KiB column windows of `nread` rows of a stripe-major
 //     [S][nrows][L] buffer read, `nwrite` rows written, nontemporal 16-byte
 //     accesses, one wave task per window, as encode_static_kernel and the
-//     pipelined repair kernel walk them (same window order, HRS_TASK_ORDER),
-//     under a few load schedules.
+//     pipelined repair kernel walk them (same window order, HRS_TASK_ORDER,
+//     and the same window map, hrs_window_map.hpp / HRS_WINDOW_SPLIT), under a
+//     few load schedules.
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
@@ -122,7 +123,7 @@ __device__ __forceinline__ u32x4 pace_work(u32x4 x) {
 
 template <int R, int W, int D, int M>
 __global__ void __launch_bounds__(256) rows_kernel(uint8_t* __restrict__ base, uint64_t nstripes, int nrows,
-                                                    uint64_t L, int order) {
+                                                    uint64_t L, int order, int split) {
   const int lane = threadIdx.x & 63;
   const uint64_t nwin = L / 2048u;
   const uint64_t ntasks = nstripes * nwin;
@@ -131,12 +132,14 @@ __global__ void __launch_bounds__(256) rows_kernel(uint8_t* __restrict__ base, u
     const uint64_t t = wt.at(j);
     if (t >= wt.end) break;
     const uint64_t s = t / nwin;
-    uint8_t* sb = base + s * nrows * L + (t - s * nwin) * 2048u + lane * 16;
+    const WindowPos wp = window_pos(t - s * nwin, nwin, split);  // the coding kernels' window map
+    const uint32_t half16 = wp.half / 16;
+    uint8_t* sb = base + s * nrows * L + wp.off + lane * 16;
     u32x4 v[R][2];
     auto ld = [&](int r) {
       const u32x4* p = reinterpret_cast<const u32x4*>(sb + (nrows - R + r) * L);
       v[r][0] = __builtin_nontemporal_load(p);
-      v[r][1] = __builtin_nontemporal_load(p + 64);
+      v[r][1] = __builtin_nontemporal_load(p + half16);
     };
 #pragma unroll
     for (int r = 0; r < D && r < R; ++r) ld(r);
@@ -153,7 +156,7 @@ __global__ void __launch_bounds__(256) rows_kernel(uint8_t* __restrict__ base, u
     for (int o = 0; o < W; ++o) {
       u32x4* q = reinterpret_cast<u32x4*>(sb + o * L);
       __builtin_nontemporal_store(a + static_cast<uint32_t>(o), q);
-      __builtin_nontemporal_store(b + static_cast<uint32_t>(o), q + 64);
+      __builtin_nontemporal_store(b + static_cast<uint32_t>(o), q + half16);
     }
   }
 }
@@ -193,13 +196,21 @@ hrs_status launch_stream(const void* src, void* dst, size_t bytes, int schedule,
   }
 }
 
+// The window map's family default by the write count, as the product picks
+// it: the (k, p) shapes of the compile-time encodes run the static encode's
+// map, every other mix is a repair on the runtime-matrix kernels.
+constexpr bool static_encode_mix(int r, int w) {
+  return (r == 10 && w == 4) || (r == 6 && w == 3) || (r == 12 && w == 4) || (r == 3 && w == 2);
+}
+
 // Schedules (rows in flight D, VALU steps per dword M): 0 = (R, 0) all loads
 // first, no math; 1 = (3, 12); 2 = (5, 6); 3 = (1, 0).
 template <int R, int W, int D, int M>
 hrs_status launch_rows_dm(void* base, size_t nstripes, int nrows, size_t L, unsigned grid, hipStream_t st) {
   auto k = rows_kernel<R, W, D, M>;
   hipLaunchKernelGGL(k, dim3(grid), dim3(256), 0, st, static_cast<uint8_t*>(base), static_cast<uint64_t>(nstripes),
-                     nrows, static_cast<uint64_t>(L), task_order(kOrderStaticEncode));
+                     nrows, static_cast<uint64_t>(L), task_order(kOrderStaticEncode),
+                     window_split(static_encode_mix(R, W) ? kSplitStaticEncode : kSplitRuntime));
   return hipGetLastError() == hipSuccess ? HRS_OK : HRS_EDEVICE;
 }
 

@@ -22,18 +22,18 @@ __global__ void __launch_bounds__(kBlockThreads) bitsliced_kernel(const RowArgs 
     if (t >= wt.end) break;
     int nin = a.nin;  // opaque per task: the r < nin predicates are not hoisted (they would spill)
     asm volatile("" : "+s"(nin));
-    const uint64_t stripe = t / a.nwin;
-    const uint64_t off = (t - stripe * a.nwin) * kWindowBytes;
+    const TaskPos tp = task_pos(a, t);
+    const uint64_t stripe = tp.stripe, off = tp.off;
     const uint64_t in_base = stripe * a.in_stride + off;
     uint32_t rows[NINB][8];
 #pragma unroll
     for (int r = 0; r < NINB; ++r)
-      if (r < nin) load_row(a.in[r] + in_base, lane, rows[r]);
+      if (r < nin) load_row(a.in[r] + in_base, lane, rows[r], tp.half);
     uint32_t acc[NOUT][8];
     if (a.accumulate) {
 #pragma unroll
       for (int o = 0; o < NOUT; ++o) {
-        load_row(a.out[o] + stripe * a.out_stride + off, lane, acc[o]);
+        load_row(a.out[o] + stripe * a.out_stride + off, lane, acc[o], tp.half);
         bitslice(acc[o]);
       }
     } else {
@@ -49,7 +49,7 @@ __global__ void __launch_bounds__(kBlockThreads) bitsliced_kernel(const RowArgs 
 #pragma unroll
     for (int o = 0; o < NOUT; ++o) {
       bitslice(acc[o]);
-      store_row(a.out[o] + stripe * a.out_stride + off, lane, acc[o]);
+      store_row(a.out[o] + stripe * a.out_stride + off, lane, acc[o], tp.half);
     }
   }
 }
@@ -62,24 +62,24 @@ __global__ void __launch_bounds__(kBlockThreads) bitsliced_kernel(const RowArgs 
 template <int NOUT, int NINB>
 __device__ __forceinline__ void load_task(const RowArgs& a, uint64_t t, int nin, int lane,
                                           uint32_t (&rows)[NINB][8]) {
-  const uint64_t stripe = t / a.nwin;
-  const uint64_t off = (t - stripe * a.nwin) * kWindowBytes;
+  const TaskPos tp = task_pos(a, t);
+  const uint64_t stripe = tp.stripe, off = tp.off;
   const uint64_t in_base = stripe * a.in_stride + off;
 #pragma unroll
   for (int r = 0; r < NINB; ++r)
-    if (r < nin) load_row(a.in[r] + in_base, lane, rows[r]);
+    if (r < nin) load_row(a.in[r] + in_base, lane, rows[r], tp.half);
 }
 
 template <int NOUT, int NINB>
 __device__ __forceinline__ void apply_task(const RowArgs& a, uint64_t t, int nin, int lane,
                                            uint32_t (&rows)[NINB][8]) {
-  const uint64_t stripe = t / a.nwin;
-  const uint64_t off = (t - stripe * a.nwin) * kWindowBytes;
+  const TaskPos tp = task_pos(a, t);
+  const uint64_t stripe = tp.stripe, off = tp.off;
   uint32_t acc[NOUT][8];
   if (a.accumulate) {
 #pragma unroll
     for (int o = 0; o < NOUT; ++o) {
-      load_row(a.out[o] + stripe * a.out_stride + off, lane, acc[o]);
+      load_row(a.out[o] + stripe * a.out_stride + off, lane, acc[o], tp.half);
       bitslice(acc[o]);
     }
   } else {
@@ -95,7 +95,7 @@ __device__ __forceinline__ void apply_task(const RowArgs& a, uint64_t t, int nin
 #pragma unroll
   for (int o = 0; o < NOUT; ++o) {
     bitslice(acc[o]);
-    store_row(a.out[o] + stripe * a.out_stride + off, lane, acc[o]);
+    store_row(a.out[o] + stripe * a.out_stride + off, lane, acc[o], tp.half);
   }
 }
 
@@ -135,11 +135,11 @@ __global__ void __launch_bounds__(kBlockThreads) bitsliced_pipe_kernel(const Row
 // pointers of group g come from the kernel arguments by a wave-uniform index
 // (scalar loads).
 template <int NOUT, int D>
-__device__ __forceinline__ void load_group(const RowArgs& a, int r0, int nin, uint64_t in_base, int lane,
-                                           uint32_t (&rows)[D][8]) {
+__device__ __forceinline__ void load_group(const RowArgs& a, int r0, int nin, uint64_t in_base, uint32_t half,
+                                           int lane, uint32_t (&rows)[D][8]) {
 #pragma unroll
   for (int j = 0; j < D; ++j)
-    if (r0 + j < nin) load_row(a.in[r0 + j] + in_base, lane, rows[j]);
+    if (r0 + j < nin) load_row(a.in[r0 + j] + in_base, lane, rows[j], half);
 }
 
 template <int NOUT, int D>
@@ -160,14 +160,14 @@ __global__ void __launch_bounds__(kBlockThreads) bitsliced_stream_kernel(const R
     if (t >= wt.end) break;
     int nin = a.nin;
     asm volatile("" : "+s"(nin));
-    const uint64_t stripe = t / a.nwin;
-    const uint64_t off = (t - stripe * a.nwin) * kWindowBytes;
+    const TaskPos tp = task_pos(a, t);
+    const uint64_t stripe = tp.stripe, off = tp.off;
     const uint64_t in_base = stripe * a.in_stride + off;
     uint32_t acc[NOUT][8];
     if (a.accumulate) {
 #pragma unroll
       for (int o = 0; o < NOUT; ++o) {
-        load_row(a.out[o] + stripe * a.out_stride + off, lane, acc[o]);
+        load_row(a.out[o] + stripe * a.out_stride + off, lane, acc[o], tp.half);
         bitslice(acc[o]);
       }
     } else {
@@ -177,19 +177,19 @@ __global__ void __launch_bounds__(kBlockThreads) bitsliced_stream_kernel(const R
         for (int q = 0; q < 8; ++q) acc[o][q] = 0u;
     }
     uint32_t ra[D][8], rb[D][8];
-    load_group<NOUT, D>(a, 0, nin, in_base, lane, ra);
+    load_group<NOUT, D>(a, 0, nin, in_base, tp.half, lane, ra);
 #pragma unroll 1
     for (int r0 = 0; r0 < nin; r0 += 2 * D) {
-      if (r0 + D < nin) load_group<NOUT, D>(a, r0 + D, nin, in_base, lane, rb);
+      if (r0 + D < nin) load_group<NOUT, D>(a, r0 + D, nin, in_base, tp.half, lane, rb);
       acc_group<NOUT, D>(a, r0, nin, acc, ra);
       if (r0 + D >= nin) break;
-      if (r0 + 2 * D < nin) load_group<NOUT, D>(a, r0 + 2 * D, nin, in_base, lane, ra);
+      if (r0 + 2 * D < nin) load_group<NOUT, D>(a, r0 + 2 * D, nin, in_base, tp.half, lane, ra);
       acc_group<NOUT, D>(a, r0 + D, nin, acc, rb);
     }
 #pragma unroll
     for (int o = 0; o < NOUT; ++o) {
       bitslice(acc[o]);
-      store_row(a.out[o] + stripe * a.out_stride + off, lane, acc[o]);
+      store_row(a.out[o] + stripe * a.out_stride + off, lane, acc[o], tp.half);
     }
   }
 }
@@ -225,7 +225,8 @@ hipError_t launch_bits_n(const RowArgs& a, hipStream_t s) {
     }
   note_kernel_t(name, NOUT, NINB);
   const int per_cu = BitLoop<NOUT, NINB>::kRolled ? 3 : 2;
-  hipLaunchKernelGGL(kern, dim3(stream_grid(a.ntasks, per_cu)), dim3(kBlockThreads), 0, s, with_order(a, kOrderRuntime));
+  hipLaunchKernelGGL(kern, dim3(stream_grid(a.ntasks, per_cu)), dim3(kBlockThreads), 0, s,
+                     with_split(with_order(a, kOrderRuntime), kSplitRuntime));
   return hipGetLastError();
 }
 
@@ -245,7 +246,8 @@ hipError_t launch_stream_n(const RowArgs& a, hipStream_t s) {
   auto kern = bitsliced_stream_kernel<NOUT, kStreamGroup>;
   note_kernel_t("bitsliced_stream_kernel", NOUT, kStreamGroup);
   const int per_cu = NOUT >= 4 ? 3 : 2;
-  hipLaunchKernelGGL(kern, dim3(stream_grid(a.ntasks, per_cu)), dim3(kBlockThreads), 0, s, with_order(a, kOrderRuntime));
+  hipLaunchKernelGGL(kern, dim3(stream_grid(a.ntasks, per_cu)), dim3(kBlockThreads), 0, s,
+                     with_split(with_order(a, kOrderRuntime), kSplitRuntime));
   return hipGetLastError();
 }
 
