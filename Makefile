@@ -26,7 +26,8 @@ API_OBJ  := $(patsubst %,build/%.o,$(API_SRC))
 JNI      := lambdafs_amd/libhrs_jni.so
 HARNESS  := tests/cpp/codec_harness tests/cpp/crc_model tests/cpp/jni_harness tests/cpp/host_logic tests/cpp/crc_tables \
             tests/cpp/copy_pool_test tests/cpp/scrub_logic tests/cpp/heal_logic tests/cpp/heal_erased_logic \
-            tests/cpp/repair_checked_logic tests/cpp/ragged_crc_model tests/cpp/window_map
+            tests/cpp/repair_checked_logic tests/cpp/ragged_crc_model tests/cpp/window_map \
+            tests/cpp/ragged_repair_crc_model
 
 TOOLS    := tools/host_call_rate tools/host_pipeline_sweep tools/host_copy_probe
 
@@ -65,7 +66,8 @@ build/hrs_probe.o: include/hrs_probe.h
 
 # `make scrub_resources`, `make scrub_crc_resources`, `make heal_erased_resources`,
 # `make heal_erased_crc_resources`, `make repair_resources`, `make ragged_resources`,
-# `make ragged_crc_resources`, `make ragged_repair_resources` (hrs_batch_ragged.hip):
+# `make ragged_crc_resources`, `make ragged_repair_resources` (hrs_batch_ragged.hip),
+# `make ragged_repair_crc_resources` (hrs_batch_ragged_crc.hip):
 # the compiler's resource report of every kernel of hrs_<name>.hip (the scrub
 # family carries no scratch). Not .PHONY: a phony target takes no pattern rule.
 %_resources: lambdafs_amd/csrc/hrs_%.hip $(HDRS)
@@ -73,12 +75,14 @@ build/hrs_probe.o: include/hrs_probe.h
 	$(HIPCC) $(HIPFLAGS) -Rpass-analysis=kernel-resource-usage -c $< -o build/hrs_$*.report.o 2>&1 | \
 	    grep -E 'Function Name|VGPRs:|SGPRs:|ScratchSize|Occupancy|LDS Size'
 
-# The ragged repair's unit is named after the batch it extends.
+# The ragged repair's units are named after the batch they extend.
 ragged_repair_resources: batch_ragged_resources
+ragged_repair_crc_resources: batch_ragged_crc_resources
 
 KOBJ     := build/hrs_kernels.o build/hrs_runtime.o build/hrs_batch.o build/hrs_crc.o build/hrs_fused.o build/hrs_decode_crc.o \
             build/hrs_batch_crc.o build/hrs_scrub.o build/hrs_scrub_crc.o build/hrs_heal_erased.o \
-            build/hrs_heal_erased_crc.o build/hrs_repair.o build/hrs_ragged.o build/hrs_ragged_crc.o build/hrs_batch_ragged.o
+            build/hrs_heal_erased_crc.o build/hrs_repair.o build/hrs_ragged.o build/hrs_ragged_crc.o build/hrs_batch_ragged.o \
+            build/hrs_batch_ragged_crc.o
 
 $(LIB): $(API_OBJ) $(KOBJ) lambdafs_amd/csrc/libhrs.map
 	$(HIPCC) $(HIPFLAGS) -shared -Wl,--version-script=lambdafs_amd/csrc/libhrs.map -o $@ $(API_OBJ) $(KOBJ) \
@@ -151,6 +155,10 @@ tests/cpp/crc_model: tests/cpp/crc_model.cpp lambdafs_amd/csrc/crc32.hpp
 tests/cpp/ragged_crc_model: tests/cpp/ragged_crc_model.cpp lambdafs_amd/csrc/crc32.hpp
 	g++ -O2 -std=c++17 -Wall -o $@ $< -lz
 
+# CPU model of the ragged repair + CRC fold (per-cell lengths, the padding taken off again) vs zlib over the cell's bytes.
+tests/cpp/ragged_repair_crc_model: tests/cpp/ragged_repair_crc_model.cpp lambdafs_amd/csrc/crc32.hpp
+	g++ -O2 -std=c++17 -Wall -o $@ $< -lz
+
 # The window map of the static encode and the runtime-matrix repairs, enumerated (host code only).
 tests/cpp/window_map: tests/cpp/window_map.cpp lambdafs_amd/csrc/hrs_window_map.hpp
 	g++ -O2 -std=c++17 -Wall -o $@ $<
@@ -167,7 +175,7 @@ HSAN     := -Xarch_host -fsanitize=address -Xarch_host -fsanitize=undefined -Xar
             -Xarch_host -fno-omit-frame-pointer
 ASAN_BIN := $(ASAN_DIR)/host_logic $(ASAN_DIR)/jni_harness $(ASAN_DIR)/codec_harness $(ASAN_DIR)/scrub_logic \
             $(ASAN_DIR)/heal_logic $(ASAN_DIR)/heal_erased_logic $(ASAN_DIR)/repair_checked_logic \
-            $(ASAN_DIR)/ragged_crc_model
+            $(ASAN_DIR)/ragged_crc_model $(ASAN_DIR)/ragged_repair_crc_model
 ASAN_LOG := profiles/r06/asan
 
 ASAN_API := $(patsubst %,$(ASAN_DIR)/%.o,$(API_SRC))
@@ -205,6 +213,10 @@ $(ASAN_DIR)/ragged_crc_model: tests/cpp/ragged_crc_model.cpp lambdafs_amd/csrc/c
 	@mkdir -p $(ASAN_DIR)
 	$(CLANG)++ $(SAN) -std=c++17 -o $@ $< -lz
 
+$(ASAN_DIR)/ragged_repair_crc_model: tests/cpp/ragged_repair_crc_model.cpp lambdafs_amd/csrc/crc32.hpp
+	@mkdir -p $(ASAN_DIR)
+	$(CLANG)++ $(SAN) -std=c++17 -o $@ $< -lz
+
 $(ASAN_DIR)/jni_harness: tests/cpp/jni_harness.c $(ASAN_DIR)/libhrs_jni.so $(ASAN_DIR)/liboracle.so
 	$(CLANG) $(SAN) -std=c11 -Iinclude -Ioracle -o $@ $< -L$(ASAN_DIR) -lhrs_jni -lhrs -loracle -lz -ldl $(ASAN_RPATH)
 
@@ -222,6 +234,7 @@ asan: $(ASAN_BIN)
 	  $(ASAN_DIR)/heal_erased_logic; \
 	  $(ASAN_DIR)/repair_checked_logic; \
 	  $(ASAN_DIR)/ragged_crc_model; \
+	  $(ASAN_DIR)/ragged_repair_crc_model; \
 	  $(ASAN_DIR)/jni_harness --cpu; \
 	  for kp in "10 4" "12 4" "6 3" "3 2"; do $(ASAN_DIR)/codec_harness --host-only $$kp; done' \
 	  > $(ASAN_LOG)/asan_run.log 2>&1 || { cat $(ASAN_LOG)/asan_run.log; exit 1; }

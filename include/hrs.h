@@ -566,7 +566,8 @@ hrs_status hrs_encode_ragged_batch_host(hrs_codec* codec, uint8_t* stripes, size
  * not a multiple of that many 2 KiB sub-windows) overrides the fused kernel's
  * window size, for tests and A/B runs.
  * Not covered, by design: the synchronous single-stripe host call, the JNI
- * overload. Ragged survivors in the repair calls: "ragged repair" below. */
+ * overload. Ragged survivors in the repair calls: "ragged repair" below; the
+ * repaired cells' CRCs, which cover no zero fill: "ragged repair + CRC-32". */
 
 /* hrs_encode_ragged_dev + the CRC-32 of all k + p cells of every stripe.
  * crc_in / crc_out: DEVICE uint32 [nstripes * (k + p)]. Asynchronous on
@@ -641,8 +642,8 @@ hrs_status hrs_encode_ragged_batch_host_crc(hrs_codec* codec, uint8_t* stripes, 
  * 3 keeps the ragged kernels even then (hrs_set_kernel_mode).
  * Not covered, by design: patterns that read more than 32 survivors (codes
  * with k > 32, which the plain call serves one stripe at a time: HRS_EINVAL
- * here), the CRC forms of the ragged repair, the JNI overloads and the
- * single-stripe host call. */
+ * here), the JNI overloads and the single-stripe host call. The CRC forms:
+ * "ragged repair + CRC-32" below. */
 
 /* hrs_decode_batch_dev's layout plus valid. Asynchronous on stream; valid is
  * copied before the call returns (in plan order, through the handle's per-call
@@ -658,6 +659,80 @@ hrs_status hrs_decode_batch_ragged_host(hrs_codec* codec, const uint8_t* stripes
                                         size_t stripe_stride, const int* erased, int max_erased, uint8_t* out,
                                         size_t out_row_stride, size_t out_stripe_stride, size_t len,
                                         size_t nstripes, const uint32_t* valid);
+
+/* ---- ragged repair + CRC-32: the checksum a repaired block is accepted by ----
+ * The reference accepts a repaired block only by its checksum:
+ * Decoder.fixErasedBlock makes a fresh CRC32 (Decoder.java:222-229),
+ * fixErasedBlockImpl updates it with crc.update(writeBufs[i], 0, toWrite),
+ * toWrite = min(bufSize, limit - written) (Decoder.java:360-369), and the
+ * value is compared with the stored block checksum. So the checksum of a
+ * repaired cell of a file's last stripe covers EXACTLY the cell's real length,
+ * with no zero fill behind it. These are the two ragged repair calls above
+ * with those CRCs from the same pass; their semantics are the product of the
+ * "ragged repair" contract and the "batches + CRC-32" rules, plus one sentence:
+ *   - every byte written to out, every byte left untouched, the survivor
+ *     choice, HRS_ETOOMANY and the code families are exactly the ragged
+ *     sibling's; valid is a HOST uint32_t[nstripes * n] in hops order, free on
+ *     return; bytes at or beyond valid never influence an output or a CRC;
+ *   - the CRC layout is hrs_decode_batch_crc_dev's, [nstripes * max_erased]:
+ *     crc_out[s * max_erased + t] belongs to output t of stripe s;
+ *   - with e = erased[s * max_erased + t], crc_out[s * max_erased + t] is the
+ *     zlib CRC-32 of the first valid[s * n + e] bytes of the rebuilt cell,
+ *     continued from crc_in[s * max_erased + t] (CRC32.update chaining; a NULL
+ *     crc_in is a fresh CRC32). NO zeros are appended (Decoder.java:360-369).
+ *     This differs on purpose from the ragged ENCODE's CRCs, which follow
+ *     Encoder.updateChecksums over the full buffer, zero fill included;
+ *   - a length of 0 continues over no bytes: crc_out = crc_in (0 without one);
+ *     the same holds for t at or past the stripe's loss count and for every
+ *     word of a stripe that lost nothing;
+ *   - crc_out may be crc_in itself; any other overlap is HRS_EINVAL.
+ * Argument rules, in this order: a NULL handle is HRS_EINVAL with no message;
+ * the sibling's argument block (stripes, out, max_erased, erased); with work
+ * to do, a NULL crc_out and then the overlap rule, both HRS_EINVAL; a NULL
+ * valid is HRS_EINVAL; len == 0, nstripes == 0 or max_erased == 0 returns
+ * HRS_OK and touches nothing, the CRC arrays included; len > UINT32_MAX or a
+ * valid entry > len is HRS_EINVAL with the stripe and location named; the
+ * plans, with the sibling's HRS_EINVAL / HRS_ETOOMANY; a pattern that reads
+ * more than 32 survivors is HRS_EINVAL; only then the device is selected
+ * (HRS_EDEVICE for a host-only handle). Argument errors come before any byte
+ * is copied. hrs_last_kernel / hrs_last_host_path behave as for the sibling;
+ * the host path is set only on success.
+ * Kernels: batches of at most 4 losses and at most 12 survivors read per
+ * stripe (8 at 4 losses), len a multiple of 2 KiB, 16-byte aligned bases and
+ * strides, kernel mode 0 or 3, take batch_ragged_crc_kernel<NOUT, NINB, 768>:
+ * the ragged repair's walk with the raw CRC of every live output window taken
+ * from the registers (the boundary window's words masked from the boundary
+ * on; a dead window costs no store, no table lookup and has no raw word; out
+ * is never read). Everything else (the row tail, unaligned layouts, more than
+ * 4 losses, 13-32 survivors, kernel modes 1 and 2) runs the ragged repair,
+ * then crc_ragged_window_kernel over the outputs up to each cell's length
+ * (which reads back only bytes the repair just wrote), and hrs_last_kernel
+ * names the ragged repair's kernel. batch_ragged_crc_fold_kernel finishes
+ * both: it joins the raw words that exist and takes the zero padding of the
+ * last word (or of the row) off again, Z_pad being invertible
+ * (lambdafs_amd/csrc/crc32.hpp). A batch whose every entry equals len takes
+ * hrs_decode_batch_crc_dev's route in kernel modes 0 and 1; mode 3 keeps the
+ * ragged kernels even then (hrs_set_kernel_mode).
+ * Not covered, by design: the JNI overloads, the single-stripe host call,
+ * patterns that read more than 32 survivors, a ragged form of the checked
+ * repair. */
+
+/* hrs_decode_batch_ragged_dev + the CRC-32 of every rebuilt cell over exactly
+ * its length. crc_in (nullable) and crc_out are DEVICE arrays of
+ * nstripes * max_erased words. Asynchronous on stream. */
+hrs_status hrs_decode_batch_ragged_crc_dev(hrs_codec* codec, const uint8_t* stripes, size_t row_stride,
+                                           size_t stripe_stride, const int* erased, int max_erased, uint8_t* out,
+                                           size_t out_row_stride, size_t out_stripe_stride, size_t len,
+                                           size_t nstripes, const uint32_t* valid, const uint32_t* crc_in,
+                                           uint32_t* crc_out, void* stream);
+
+/* hrs_decode_batch_ragged_host + the same CRCs; crc_in / crc_out are HOST
+ * arrays. Synchronous. */
+hrs_status hrs_decode_batch_ragged_host_crc(hrs_codec* codec, const uint8_t* stripes, size_t row_stride,
+                                            size_t stripe_stride, const int* erased, int max_erased, uint8_t* out,
+                                            size_t out_row_stride, size_t out_stripe_stride, size_t len,
+                                            size_t nstripes, const uint32_t* valid, const uint32_t* crc_in,
+                                            uint32_t* crc_out);
 
 /* ---- stripe scrubbing: ReedSolomonCode.computeErrorLocations in bulk ----
  * Whether a stripe at rest is still a codeword, and which cells went bad when
@@ -1048,7 +1123,14 @@ hrs_status hrs_repair_checked_host(const hrs_codec* codec, uint8_t* const* rows,
  * len to the plain batch's route (which then follows its own mode) and any
  * other batch to the ragged kernels, batch_ragged_kernel where the shape has
  * one; 2 forces batch_ragged_bytewise_kernel for every batch; 3 keeps the
- * ragged kernels for an all-full batch too. */
+ * ragged kernels for an all-full batch too.
+ * The ragged repair + CRC calls: 0 and 1 send an all-full batch to
+ * hrs_decode_batch_crc_dev's route with the plans already built (the CRC over
+ * len bytes then is the CRC over valid bytes); for any other batch 0 and 3
+ * take batch_ragged_crc_kernel where the shape has one, 1 and 2 never fuse
+ * (ragged repair, crc_ragged_window_kernel over the outputs, fold), 2 with
+ * the byte-granular repair; 3 keeps the ragged kernels for an all-full batch
+ * too. With nothing lost anywhere only the fold runs. */
 hrs_status hrs_set_kernel_mode(hrs_codec* codec, int mode);
 
 #ifdef __cplusplus

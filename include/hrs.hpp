@@ -279,6 +279,26 @@ class HipCode : public ErasureCode {
           h_);
   }
 
+  // The ragged repair with the CRC-32 of every rebuilt cell over exactly its
+  // length, no zero fill behind it (hrs_decode_batch_ragged_crc_dev: DEVICE crc
+  // arrays; hrs_decode_batch_ragged_host_crc: HOST ones; [nstripes * maxErased]).
+  void decodeBatchRaggedCrcDev(const uint8_t* stripes, size_t rowStride, size_t stripeStride, const int* erased,
+                               int maxErased, uint8_t* out, size_t outRowStride, size_t outStripeStride, size_t len,
+                               size_t nstripes, const uint32_t* valid, const uint32_t* crcIn, uint32_t* crcOut,
+                               void* stream) {
+    check(hrs_decode_batch_ragged_crc_dev(h_, stripes, rowStride, stripeStride, erased, maxErased, out, outRowStride,
+                                          outStripeStride, len, nstripes, valid, crcIn, crcOut, stream),
+          h_);
+  }
+
+  void decodeBatchRaggedHostCrc(const uint8_t* stripes, size_t rowStride, size_t stripeStride, const int* erased,
+                                int maxErased, uint8_t* out, size_t outRowStride, size_t outStripeStride, size_t len,
+                                size_t nstripes, const uint32_t* valid, const uint32_t* crcIn, uint32_t* crcOut) {
+    check(hrs_decode_batch_ragged_host_crc(h_, stripes, rowStride, stripeStride, erased, maxErased, out, outRowStride,
+                                           outStripeStride, len, nstripes, valid, crcIn, crcOut),
+          h_);
+  }
+
   // RS-specific decodeBulk(readBufs, writeBufs, erasedLocation), ReedSolomonCode.java:168-185.
   void decodeBulk3(const std::vector<uint8_t*>& readBufs, const std::vector<uint8_t*>& writeBufs, size_t len,
                    const std::vector<int>& erased) {

@@ -53,6 +53,7 @@ EXPORTS = (
     "hrs_encode_ragged_dev", "hrs_encode_ragged_batch_host",
     "hrs_encode_ragged_crc_dev", "hrs_encode_ragged_batch_host_crc",
     "hrs_decode_batch_ragged_dev", "hrs_decode_batch_ragged_host",
+    "hrs_decode_batch_ragged_crc_dev", "hrs_decode_batch_ragged_host_crc",
 )
 # include/hrs_probe.h, exported by libhrs_probe.so
 PROBE_EXPORTS = ("hrs_probe_stream", "hrs_probe_rows")
@@ -158,6 +159,8 @@ def lib():
         "hrs_encode_ragged_batch_host_crc": ([P, P, S, S, S, S, P, P, P], I),
         "hrs_decode_batch_ragged_dev": ([P, P, S, S, P, I, P, S, S, S, S, P, P], I),
         "hrs_decode_batch_ragged_host": ([P, P, S, S, P, I, P, S, S, S, S, P], I),
+        "hrs_decode_batch_ragged_crc_dev": ([P, P, S, S, P, I, P, S, S, S, S, P, P, P, P], I),
+        "hrs_decode_batch_ragged_host_crc": ([P, P, S, S, P, I, P, S, S, S, S, P, P, P], I),
     }
     for name, (args, res) in sigs.items():
         if os.environ.get("HRS_LIB") and not hasattr(L, name):

@@ -103,5 +103,65 @@ inline void to_tables(const Mat& m, uint32_t* out /* 4 x 256 */) {
     for (uint32_t v = 0; v < 256; ++v) out[b * 256 + v] = apply(m, v << (8 * b));
 }
 
+// ---- Z_n as a field element (host and device; the ragged repair's fold,
+// hrs_batch_ragged_crc.hip, and its CPU model tests/cpp/ragged_repair_crc_model.cpp)
+//
+// A raw CRC state is a polynomial modulo the CRC polynomial, bit 31 the
+// constant term (the reflected form), and Z_n is multiplication by x^(8n). The
+// CRC polynomial's constant term is 1, so x is invertible and so is every Z_n:
+// a raw CRC taken over a message followed by `pad` zero bytes,
+// R_pad = raw(M || 0^pad) = Z_pad(raw(M)), gives the CRC of M alone as
+//   crc(prev || M) = Z_pad^-1( Z_{|M|+pad}(crc_prev ^ ~0) ^ R_pad ) ^ ~0.
+#if defined(__HIPCC__)
+#define HRS_CRC_HD __host__ __device__
+#else
+#define HRS_CRC_HD
+#endif
+
+constexpr uint32_t kOne = 0x80000000u;   // x^0
+constexpr uint32_t kXInv = 0xDB710641u;  // x^-1: (1 ^ P) / x, P's constant term being 1
+
+// a * b modulo the CRC polynomial: 32 shift-and-add steps.
+HRS_CRC_HD constexpr uint32_t mulmod(uint32_t a, uint32_t b) {
+  uint32_t p = 0;
+  for (int i = 0; i < 32; ++i) {
+    if (a & (kOne >> i)) p ^= b;
+    b = (b & 1u) ? (b >> 1) ^ kPoly : b >> 1;
+  }
+  return p;
+}
+
+// up[j] = x^(8 * 2^j), down[j] = x^(-8 * 2^j).
+struct Pow8 {
+  uint32_t up[32];
+  uint32_t down[32];
+};
+constexpr Pow8 make_pow8() {
+  Pow8 t{};
+  uint32_t u = kOne >> 8, d = kXInv;
+  for (int i = 0; i < 3; ++i) d = mulmod(d, d);  // x^-8
+  for (int j = 0; j < 32; ++j) {
+    t.up[j] = u;
+    t.down[j] = d;
+    u = mulmod(u, u);
+    d = mulmod(d, d);
+  }
+  return t;
+}
+
+// x^(8n) (inverse: x^(-8n)), n < 2^32: the product of the constants of n's set bits.
+HRS_CRC_HD inline uint32_t xpow8(uint32_t n, bool inverse = false) {
+  constexpr Pow8 kPow8 = make_pow8();
+  uint32_t r = kOne;
+  for (int j = 0; n; ++j, n >>= 1)
+    if (n & 1u) r = mulmod(r, inverse ? kPow8.down[j] : kPow8.up[j]);
+  return r;
+}
+
+// The CRC-32 of prev || M from r_pad = raw(M || 0^pad), total = |M| + pad, `start` the CRC of prev.
+HRS_CRC_HD inline uint32_t unpad(uint32_t start, uint32_t r_pad, uint32_t total, uint32_t pad) {
+  return mulmod(xpow8(pad, true), mulmod(xpow8(total), start ^ 0xFFFFFFFFu) ^ r_pad) ^ 0xFFFFFFFFu;
+}
+
 }  // namespace crc
 }  // namespace hrs

@@ -1,7 +1,8 @@
 // Device-resident repair batches: heterogeneous batches (one erasure pattern
 // per stripe, plans uploaded through pinned slots, one batch launch) with
 // their block-CRC-32 form (hrs_decode_batch_dev, hrs_decode_batch_crc_dev)
-// and their ragged form (hrs_decode_batch_ragged_dev: per-cell lengths),
+// and their ragged forms (hrs_decode_batch_ragged_dev: per-cell lengths;
+// hrs_decode_batch_ragged_crc_dev: with each rebuilt cell's CRC-32 over its length),
 // and the per-call table slots every unit uploads through. The host-memory
 // batches that run their chunks through run_batch are in hrs_hostbatch_api.cpp.
 #include <hip/hip_runtime.h>
@@ -17,6 +18,7 @@
 #include "hrs_crc.hpp"
 #include "hrs_internal.hpp"
 #include "hrs_launch.hpp"
+#include "hrs_ragged.hpp"
 
 namespace hrs::api {
 
@@ -138,13 +140,18 @@ hrs::BatchArgs batch_args(const BatchPlanSet& ps, const BatchGeom& g, size_t s0)
 // The ragged launches of stripes [s0, s0 + ns): batch_ragged_kernel over the
 // whole 2 KiB windows of an aligned batch of its shapes, the byte-granular
 // kernel over the row tail, every other shape or layout and kernel mode 2.
-hrs_status launch_batch_ragged(hrs_codec* c, const BatchPlanSet& ps, const BatchGeom& g, size_t s0, size_t ns,
-                               hipStream_t hs) {
+hrs::BatchRaggedArgs batch_ragged_args(const BatchPlanSet& ps, const BatchGeom& g, size_t s0) {
   hrs::BatchRaggedArgs a{};
   a.b = batch_args(ps, g, s0);
   a.lens = ps.dlens + s0 * static_cast<size_t>(ps.len_words);
   a.words = ps.len_words;
   a.nin_words = ps.max_nin;
+  return a;
+}
+
+hrs_status launch_batch_ragged(hrs_codec* c, const BatchPlanSet& ps, const BatchGeom& g, size_t s0, size_t ns,
+                               hipStream_t hs) {
+  hrs::BatchRaggedArgs a = batch_ragged_args(ps, g, s0);
   const bool vec = c->kernel_mode != 2 && vector_aligned(g) && hrs::batch_ragged_vector_shape(ps.max_nout, ps.max_nin);
   a.b.nwin = vec ? g.len / hrs::kWindowBytes : 0;
   if (a.b.nwin > 0) {
@@ -243,13 +250,91 @@ hrs_status launch_batch_crc(hrs_codec* c, const BatchPlanSet& ps, const BatchGeo
   return fold(hrs::kCrcWindow);
 }
 
+// launch_batch(ragged) + the CRC-32 of every repaired cell over exactly its
+// length (include/hrs.h, "ragged repair + CRC-32"). The lengths the kernels and
+// the fold read are the output words of the plan-order table (ps.dlens), which
+// are 0 past a stripe's losses. One pass (batch_ragged_crc_kernel) for aligned
+// whole-window batches of the fused shapes in kernel modes 0 and 3; else the
+// ragged repair (its kernel names the call), the ragged CRC window pass over
+// the max_nout output rows up to each cell's length (it reads back only bytes
+// the repair just wrote) and the same fold with the row's padding.
+hrs_status launch_batch_ragged_crc(hrs_codec* c, const BatchPlanSet& ps, const BatchGeom& g, size_t s0, size_t ns,
+                                   const BatchCrcs& crc, hipStream_t hs, uint32_t* raw) {
+  const hrs::BatchRaggedArgs ra = batch_ragged_args(ps, g, s0);
+  auto fold = [&](uint64_t win) -> hrs_status {
+    hrs_codec::FoldTables* ft = nullptr;
+    hrs_status st = crc_fold_tables(c, g.len, win, &ft);
+    if (st != HRS_OK) return st;
+    hrs::BatchRaggedCrcFoldArgs b{};
+    b.f.raw = raw;
+    b.f.nwin = g.len / win;
+    b.f.tail = g.len % win;
+    b.f.nsr = ns * static_cast<uint64_t>(crc.max_erased);
+    b.f.G = static_cast<int>((b.f.nwin + 63) / 64);
+    b.f.tables = ft->dev;
+    b.f.crc_in = crc.in;
+    b.f.crc_out = crc.out;
+    b.lens = ra.lens;
+    b.words = ra.words;
+    b.nin_words = ra.nin_words;
+    b.max_nout = ps.max_nout;
+    b.rows_per_stripe = crc.max_erased;
+    b.len = static_cast<uint32_t>(g.len);
+    b.fused = win == static_cast<uint64_t>(hrs::kWindowBytes);
+    const hipError_t e = hrs::launch_batch_ragged_crc_fold(b, hrs::device_cu_count(), hs);
+    if (e != hipSuccess) return hip_fail(c, e, "ragged crc fold launch");
+    return fold_tables_used(c, ft, hs);
+  };
+  if (apply_crc_one_pass(c, ps.max_nout, ps.max_nin, g.len) && vector_aligned(g)) {
+    hrs_status st = crc_window_tables(c);
+    if (st != HRS_OK) return st;
+    hrs::BatchRaggedCrcArgs d{};
+    d.r = ra;
+    d.r.b.nwin = g.len / hrs::kWindowBytes;
+    d.r.b.ntasks = d.r.b.nwin * ns;
+    d.raw = raw;
+    d.tables = c->crc_tables_a;
+    d.rows_per_stripe = crc.max_erased;
+    const hipError_t e = hrs::launch_batch_ragged_crc(d, ps.max_nout, ps.max_nin, hrs::device_cu_count(), hs);
+    if (e != hipSuccess) return hip_fail(c, e, "ragged batch decode+crc launch");
+    c->last_kernel = hrs::last_kernel();
+    return fold(hrs::kWindowBytes);
+  }
+  hrs_status st = launch_batch_ragged(c, ps, g, s0, ns, hs);
+  if (st != HRS_OK) return st;
+  if ((st = crc_window_tables(c)) != HRS_OK) return st;
+  hrs::RaggedCrcWinArgs w{};
+  w.w.nrows = ps.max_nout;
+  bool aligned = aligned16(g.out) && g.out_row_stride % 16 == 0 && g.out_stripe_stride % 16 == 0;
+  for (int t = 0; t < ps.max_nout; ++t) {
+    w.w.rows[t] = g.out + static_cast<size_t>(t) * g.out_row_stride;
+    w.w.stride[t] = g.out_stripe_stride;
+  }
+  w.w.row0 = 0;
+  w.w.nrows_total = crc.max_erased;
+  w.w.len = g.len;
+  w.w.nwin = g.len / hrs::kCrcWindow;
+  w.w.tail = g.len % hrs::kCrcWindow;
+  w.w.nstripes = ns;
+  w.w.raw = raw;
+  w.w.tables = c->crc_tables_a;
+  // row t of stripe i is cut at the table's output word t: lens[i * words + nin_words + t]
+  w.valid = ra.lens + ra.nin_words;
+  w.k = ra.words;
+  const hipError_t e = hrs::launch_crc_ragged_windows(w, aligned, hrs::device_cu_count(), hs);
+  if (e != hipSuccess) return hip_fail(c, e, "ragged crc window launch");
+  return fold(hrs::kCrcWindow);  // the repair's kernel names the call
+}
+
 }  // namespace
 
 hrs_status run_batch(hrs_codec* c, const BatchPlanSet& ps, const BatchGeom& g, size_t s0, size_t ns,
                      const BatchCrcs* crc, hipStream_t s, bool ragged) {
   if (!crc) return launch_batch(c, ps, g, s0, ns, s, ragged);
-  return with_crc_scratch(c, crc_raw_bytes_for(g.len, ns, crc->max_erased), s,
-                          [&] { return launch_batch_crc(c, ps, g, s0, ns, *crc, s, c->crc_raw); });
+  return with_crc_scratch(c, crc_raw_bytes_for(g.len, ns, crc->max_erased), s, [&] {
+    return ragged ? launch_batch_ragged_crc(c, ps, g, s0, ns, *crc, s, c->crc_raw)
+                  : launch_batch_crc(c, ps, g, s0, ns, *crc, s, c->crc_raw);
+  });
 }
 
 hrs_status upload(hrs_codec* c, const void* a, size_t a_bytes, const void* b, size_t b_bytes, hipStream_t s,
@@ -324,9 +409,10 @@ hrs_status decode_batch_args_ok(hrs_codec* c, const BatchGeom& g, const int* era
 }
 
 hrs_status ragged_batch_args_ok(hrs_codec* c, const BatchGeom& g, const int* erased, int max_erased, size_t nstripes,
-                                const uint32_t* valid, BatchPlanSet& ps, bool* empty, bool* all_full) {
+                                const uint32_t* valid, BatchPlanSet& ps, bool* empty, bool* all_full, unsigned flags,
+                                const uint32_t* crc_in, const uint32_t* crc_out) {
   *all_full = false;
-  hrs_status st = decode_batch_args_ok(c, g, erased, max_erased, nstripes, 0u, nullptr, nullptr, empty);
+  hrs_status st = decode_batch_args_ok(c, g, erased, max_erased, nstripes, flags, crc_in, crc_out, empty);
   if (st != HRS_OK) return st;
   if (!valid) return fail(c, HRS_EINVAL, "valid is NULL");
   if (*empty) return HRS_OK;
@@ -392,24 +478,29 @@ hrs_status decode_batch_dev_entry(hrs_codec* c, const BatchGeom& g, const int* e
   return st;
 }
 
-// hrs_decode_batch_ragged_dev: the sibling's entry with a length per cell.
-// valid is read on the host and leaves in plan order with the plans' upload,
-// so the caller may reuse it when the call returns.
+// hrs_decode_batch_ragged_dev and hrs_decode_batch_ragged_crc_dev (with_crc;
+// DEVICE arrays): the sibling's entry with a length per cell. valid is read on
+// the host and leaves in plan order with the plans' upload, so the caller may
+// reuse it when the call returns. With CRCs a batch that lost nothing anywhere
+// still runs the plain batch's fold (every CRC continues over no bytes).
 hrs_status decode_batch_ragged_dev_entry(hrs_codec* c, const BatchGeom& g, const int* erased, int max_erased,
-                                         size_t nstripes, const uint32_t* valid, void* stream) {
+                                         size_t nstripes, const uint32_t* valid, bool with_crc, const uint32_t* crc_in,
+                                         uint32_t* crc_out, void* stream) {
   if (!c) return HRS_EINVAL;
   BatchPlanSet ps;
   bool empty = false, all_full = false;
-  hrs_status st = ragged_batch_args_ok(c, g, erased, max_erased, nstripes, valid, ps, &empty, &all_full);
+  hrs_status st = ragged_batch_args_ok(c, g, erased, max_erased, nstripes, valid, ps, &empty, &all_full,
+                                       with_crc ? kBatchWithCrc : 0u, crc_in, crc_out);
   if (st != HRS_OK || empty) return st;
   DeviceGuard guard(c->device);
   if (!guard.ok) return fail(c, HRS_EDEVICE, "cannot select HIP device %d", c->device);
-  if (ps.max_nout == 0) return HRS_OK;
-  const bool ragged = !ragged_batch_takes_plain(c, all_full);
+  if (ps.max_nout == 0 && !with_crc) return HRS_OK;
+  const bool ragged = ps.max_nout > 0 && !ragged_batch_takes_plain(c, all_full);
   if (ragged) plan_order_lengths(c, erased, max_erased, nstripes, valid, ps);
   const hipStream_t hs = static_cast<hipStream_t>(stream);
   if ((st = upload_plans(c, ps, hs)) != HRS_OK) return st;
-  st = run_batch(c, ps, g, 0, nstripes, nullptr, hs, ragged);
+  const BatchCrcs crc{max_erased, crc_in, crc_out};
+  st = run_batch(c, ps, g, 0, nstripes, with_crc ? &crc : nullptr, hs, ragged);
   slot_used(ps.slot, hs);
   return st;
 }
@@ -424,7 +515,17 @@ hrs_status hrs_decode_batch_ragged_dev(hrs_codec* c, const uint8_t* stripes, siz
                                        void* stream) {
   return decode_batch_ragged_dev_entry(
       c, {stripes, row_stride, stripe_stride, out, out_row_stride, out_stripe_stride, len}, erased, max_erased,
-      nstripes, valid, stream);
+      nstripes, valid, false, nullptr, nullptr, stream);
+}
+
+hrs_status hrs_decode_batch_ragged_crc_dev(hrs_codec* c, const uint8_t* stripes, size_t row_stride,
+                                           size_t stripe_stride, const int* erased, int max_erased, uint8_t* out,
+                                           size_t out_row_stride, size_t out_stripe_stride, size_t len,
+                                           size_t nstripes, const uint32_t* valid, const uint32_t* crc_in,
+                                           uint32_t* crc_out, void* stream) {
+  return decode_batch_ragged_dev_entry(
+      c, {stripes, row_stride, stripe_stride, out, out_row_stride, out_stripe_stride, len}, erased, max_erased,
+      nstripes, valid, true, crc_in, crc_out, stream);
 }
 
 hrs_status hrs_decode_batch_dev(hrs_codec* c, const uint8_t* stripes, size_t row_stride, size_t stripe_stride,

@@ -32,43 +32,6 @@ __constant__ gf::Tables d_batch_ragged_tables = gf::make_tables();
 
 typedef const __attribute__((address_space(4))) BatchPlan* ConstPlanPtr;
 
-// Bytes of a cell of length v inside the window [lo, lo + 2 KiB): 0 dead,
-// 2048 full, else the boundary.
-__device__ __forceinline__ uint32_t window_live(uint32_t v, uint32_t lo) {
-  const uint32_t d = v > lo ? v - lo : 0u;
-  return d < kWindowBytes ? d : kWindowBytes;
-}
-
-// store_row of the bytes below `nbytes` (0 < nbytes < 2 KiB) of the window: a
-// lane's 16-byte piece wholly below the boundary goes out as a vector, the one
-// straddling piece as whole words and then single bytes of exactly the bytes
-// below it (no read-modify-write), a piece at or beyond it not at all.
-__device__ __forceinline__ void store_row_below(uint8_t* p, int lane, const uint32_t (&w)[8], uint32_t nbytes) {
-#pragma unroll
-  for (int h = 0; h < 2; ++h) {
-    const int at = h * 1024 + lane * 16;
-    const int nb = static_cast<int>(nbytes) - at;  // bytes of this piece below the boundary
-    uint8_t* q = p + at;
-    if (nb >= 16) {
-      const u32x4 x = {w[4 * h], w[4 * h + 1], w[4 * h + 2], w[4 * h + 3]};
-      __builtin_nontemporal_store(x, reinterpret_cast<u32x4*>(q));
-    } else if (nb > 0) {
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const int rem = nb - 4 * j;
-        const uint32_t x = w[4 * h + j];
-        if (rem >= 4) {
-          *reinterpret_cast<uint32_t*>(q + 4 * j) = x;
-        } else {
-#pragma unroll
-          for (int b = 0; b < 3; ++b)
-            if (b < rem) q[4 * j + b] = static_cast<uint8_t>(x >> (8 * b));
-        }
-      }
-    }
-  }
-}
-
 // Rows whose loads are in flight together: all NINB of the plan, as in
 // batch_bitsliced_kernel (no instantiation needs scratch for it: `make
 // ragged_repair_resources`; groups of NINB / 2 rows ran the full batch 26 %

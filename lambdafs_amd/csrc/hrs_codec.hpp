@@ -450,8 +450,9 @@ struct BatchCrcs {
 // crc != NULL: with their CRCs, through the handle's raw-CRC scratch (taken and
 // released on s); the plans must have been uploaded. Without CRCs they must
 // have been when ps.fused (else: one run_apply per stripe).
-// ragged (no CRCs, ps.fused, ps.lens uploaded): the ragged kernels
-// (hrs_batch_ragged.hip) with the stripes' slice of the length table.
+// ragged (ps.fused, ps.lens uploaded): the ragged kernels
+// (hrs_batch_ragged.hip; with CRCs hrs_batch_ragged_crc.hip, each CRC over
+// exactly its cell's length) with the stripes' slice of the length table.
 hrs_status run_batch(hrs_codec* c, const BatchPlanSet& ps, const BatchGeom& g, size_t s0, size_t ns,
                      const BatchCrcs* crc, hipStream_t s, bool ragged = false);
 // The argument rules of the decode-batch entry points, in this order: the
@@ -469,9 +470,13 @@ hrs_status decode_batch_args_ok(hrs_codec* c, const BatchGeom& g, const int* era
 // empty batch (*empty = true: return HRS_OK and touch nothing), len <=
 // UINT32_MAX and every one of the nstripes * n HOST words of `valid` <= len
 // (the stripe and location named), the plans, and no pattern beyond the batch
-// kernels' kBatchMaxIn survivors. *all_full: every word equals len.
+// kernels' kBatchMaxIn survivors. *all_full: every word equals len. The CRC
+// forms pass kBatchWithCrc and their arrays on to decode_batch_args_ok, whose
+// crc_args_ok then stands between the argument block and `valid`.
 hrs_status ragged_batch_args_ok(hrs_codec* c, const BatchGeom& g, const int* erased, int max_erased, size_t nstripes,
-                                const uint32_t* valid, BatchPlanSet& ps, bool* empty, bool* all_full);
+                                const uint32_t* valid, BatchPlanSet& ps, bool* empty, bool* all_full,
+                                unsigned flags = 0u, const uint32_t* crc_in = nullptr,
+                                const uint32_t* crc_out = nullptr);
 // Whether a ragged repair batch takes the plain batch's route: every cell
 // full, in kernel modes 0 and 1 (2 and 3 keep the ragged kernels).
 inline bool ragged_batch_takes_plain(const hrs_codec* c, bool all_full) {

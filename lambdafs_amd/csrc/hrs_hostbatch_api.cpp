@@ -1,7 +1,7 @@
 // Host-memory batches (hrs_decode_batch_host, hrs_encode_batch_host, the
 // scrub / heal / heal-erased host batches, each with its block-CRC-32 form,
-// the ragged encodes hrs_encode_ragged_batch_host[_crc] and the ragged repair
-// hrs_decode_batch_ragged_host):
+// the ragged encodes hrs_encode_ragged_batch_host[_crc] and the ragged repairs
+// hrs_decode_batch_ragged_host[_crc]):
 // memory classification and the zero-copy knobs, the chunk pipeline (chunks of
 // stripes through a ring of device slots, H2D of exactly the rows read, D2H of
 // exactly the rows written), its three jobs, and the device sets. The repair
@@ -539,8 +539,9 @@ hrs_status host_batch_call(hrs_codec* c, const void* stripes, size_t span, const
 // of nstripes * max_erased words). Pinned stripes and outputs: one batch launch
 // whose kernels read the survivors and write the repaired cells across the
 // host link directly (zero copy), the plans going up first on the same stream.
-// The batch after its argument rules, its plans built. valid != NULL (no CRCs;
-// hrs_decode_batch_ragged_host): cell l of stripe s holds valid[s * n + l]
+// The batch after its argument rules, its plans built. valid != NULL
+// (hrs_decode_batch_ragged_host; with_crc too: hrs_decode_batch_ragged_host_crc,
+// each CRC over exactly its cell's length): cell l of stripe s holds valid[s * n + l]
 // leading bytes; the length table goes up with the plans, a staged chunk
 // copies in only those bytes of each survivor and copies back only those of
 // each output, and what the slot images keep behind them the ragged kernels
@@ -640,18 +641,22 @@ hrs_status decode_batch_host_entry(hrs_codec* c, const BatchGeom& g, const int* 
   return decode_batch_host_run(c, g, erased, max_erased, nstripes, ps, with_crc, crc_in, crc_out, nullptr);
 }
 
-// hrs_decode_batch_ragged_host: rules 1-7, then the sibling's job with the
+// hrs_decode_batch_ragged_host and hrs_decode_batch_ragged_host_crc (with_crc;
+// HOST arrays of nstripes * max_erased words, each CRC over exactly its cell's
+// length): the rules of ragged_batch_args_ok, then the sibling's job with the
 // lengths; an all-full batch in kernel modes 0 and 1 is the sibling's job.
 hrs_status decode_batch_ragged_host_entry(hrs_codec* c, const BatchGeom& g, const int* erased, int max_erased,
-                                          size_t nstripes, const uint32_t* valid) {
+                                          size_t nstripes, const uint32_t* valid, bool with_crc = false,
+                                          const uint32_t* crc_in = nullptr, uint32_t* crc_out = nullptr) {
   if (!c) return HRS_EINVAL;
   BatchPlanSet ps;
   bool empty = false, all_full = false;
-  const hrs_status st = ragged_batch_args_ok(c, g, erased, max_erased, nstripes, valid, ps, &empty, &all_full);
+  const hrs_status st = ragged_batch_args_ok(c, g, erased, max_erased, nstripes, valid, ps, &empty, &all_full,
+                                             with_crc ? kBatchWithCrc : 0u, crc_in, crc_out);
   if (st != HRS_OK || empty) return st;
   const bool ragged = ps.max_nout > 0 && !ragged_batch_takes_plain(c, all_full);
   if (ragged) plan_order_lengths(c, erased, max_erased, nstripes, valid, ps);
-  return decode_batch_host_run(c, g, erased, max_erased, nstripes, ps, false, nullptr, nullptr,
+  return decode_batch_host_run(c, g, erased, max_erased, nstripes, ps, with_crc, crc_in, crc_out,
                                ragged ? valid : nullptr);
 }
 
@@ -1045,6 +1050,16 @@ hrs_status hrs_decode_batch_ragged_host(hrs_codec* c, const uint8_t* stripes, si
   return decode_batch_ragged_host_entry(
       c, {stripes, row_stride, stripe_stride, out, out_row_stride, out_stripe_stride, len}, erased, max_erased,
       nstripes, valid);
+}
+
+hrs_status hrs_decode_batch_ragged_host_crc(hrs_codec* c, const uint8_t* stripes, size_t row_stride,
+                                            size_t stripe_stride, const int* erased, int max_erased, uint8_t* out,
+                                            size_t out_row_stride, size_t out_stripe_stride, size_t len,
+                                            size_t nstripes, const uint32_t* valid, const uint32_t* crc_in,
+                                            uint32_t* crc_out) {
+  return decode_batch_ragged_host_entry(
+      c, {stripes, row_stride, stripe_stride, out, out_row_stride, out_stripe_stride, len}, erased, max_erased,
+      nstripes, valid, true, crc_in, crc_out);
 }
 
 hrs_status hrs_encode_batch_host(hrs_codec* c, uint8_t* stripes, size_t row_stride, size_t stripe_stride, size_t len,

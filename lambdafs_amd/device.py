@@ -302,9 +302,15 @@ def _decode_batch(code, stripes, erased, out, crcs=None, valid=None):
             out.data_ptr(), out.stride(1), out.stride(0), L, S)
     if valid is not None:
         v = _ragged_valid(code, valid, S, n)
+        if crcs is None:
+            if L and S:
+                code._check(_lib.lib().hrs_decode_batch_ragged_dev(*args, v.ctypes.data, _stream(stripes)))
+            return None
+        cin, crc = _dev_crcs((S, e.shape[1]), stripes, L, S, *crcs)
         if L and S:
-            code._check(_lib.lib().hrs_decode_batch_ragged_dev(*args, v.ctypes.data, _stream(stripes)))
-        return None
+            code._check(_lib.lib().hrs_decode_batch_ragged_crc_dev(*args, v.ctypes.data, cin, crc.data_ptr(),
+                                                                   _stream(stripes)))
+        return crc
     if crcs is None:
         if L and S:
             code._check(_lib.lib().hrs_decode_batch_dev(*args, _stream(stripes)))
@@ -346,6 +352,17 @@ def decode_batch_ragged(code, stripes, erased, out, valid):
     _decode_batch(code, stripes, erased, out, valid=valid)
 
 
+def decode_batch_ragged_crc(code, stripes, erased, out, valid, crc_in=None, crc_out=None):
+    """decode_batch_ragged plus the CRC-32 of every rebuilt cell from the same
+    pass (hrs_decode_batch_ragged_crc_dev), as Decoder.fixErasedBlockImpl takes
+    it: entry [s, t] of the returned int32 tensor [S, E] is the CRC of exactly
+    the first valid[s, erased[s, t]] bytes of output t of stripe s, with no
+    zeros behind them, continued from crc_in[s, t]. An entry of length 0 or
+    past its stripe's losses keeps its crc_in value (0 without crc_in).
+    crc_out: the tensor to fill and return (it may be crc_in itself)."""
+    return _decode_batch(code, stripes, erased, out, (crc_in, crc_out), valid=valid)
+
+
 # ---- encode and decode over host batches
 
 def _decode_batch_host(code, head, call, stripes, erased, out, crcs=None, valid=None):
@@ -357,8 +374,12 @@ def _decode_batch_host(code, head, call, stripes, erased, out, crcs=None, valid=
     args = (*head, sp, row_stride, stripe_stride, e.ctypes.data, e.shape[1], *_host_out(out, S, e.shape[1], L), L, S)
     if valid is not None:
         v = _ragged_valid(code, valid, S, code.stripeSize() + code.paritySize())
-        code._check(call(*args, v.ctypes.data))
-        return None
+        if crcs is None:
+            code._check(call(*args, v.ctypes.data))
+            return None
+        cin, crc = _host_crcs((S, e.shape[1]), L, *crcs)
+        code._check(call(*args, v.ctypes.data, cin, crc.ctypes.data))
+        return crc
     if crcs is None:
         code._check(call(*args))
         return None
@@ -395,6 +416,14 @@ def decode_batch_host_ragged(code, stripes, erased, out, valid):
     repaired cell are copied back."""
     _decode_batch_host(code, (code._handle(),), _lib.lib().hrs_decode_batch_ragged_host, stripes, erased, out,
                        valid=valid)
+
+
+def decode_batch_host_ragged_crc(code, stripes, erased, out, valid, crc_in=None, crc_out=None):
+    """hrs_decode_batch_ragged_host_crc: decode_batch_host_ragged plus
+    decode_batch_ragged_crc's CRCs, as a uint32 numpy array [S, E] (crc_in and
+    crc_out: such arrays; crc_out may be crc_in itself)."""
+    return _decode_batch_host(code, (code._handle(),), _lib.lib().hrs_decode_batch_ragged_host_crc, stripes, erased,
+                              out, (crc_in, crc_out), valid=valid)
 
 
 def encode_batch_host(code, stripes):
