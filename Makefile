@@ -15,7 +15,7 @@ HDRS     := Makefile include/hrs.h lambdafs_amd/csrc/hrs_device.hpp lambdafs_amd
             lambdafs_amd/csrc/hrs_heal_erased_device.hpp \
             lambdafs_amd/csrc/hrs_scrub_device.hpp lambdafs_amd/csrc/hrs_repair.hpp lambdafs_amd/csrc/hrs_repair_rule.hpp \
             lambdafs_amd/csrc/hrs_ragged.hpp lambdafs_amd/csrc/hrs_ragged_device.hpp lambdafs_amd/csrc/hrs_batch_ragged.hpp \
-            lambdafs_amd/csrc/hrs_window_map.hpp
+            lambdafs_amd/csrc/hrs_window_map.hpp lambdafs_amd/csrc/hrs_scrub_ragged.hpp
 
 # Host translation units of the C ABI (no kernels): lifecycle + queries,
 # matrices, device dispatch, the CRC-32 service, host-buffer path, repair
@@ -27,7 +27,7 @@ JNI      := lambdafs_amd/libhrs_jni.so
 HARNESS  := tests/cpp/codec_harness tests/cpp/crc_model tests/cpp/jni_harness tests/cpp/host_logic tests/cpp/crc_tables \
             tests/cpp/copy_pool_test tests/cpp/scrub_logic tests/cpp/heal_logic tests/cpp/heal_erased_logic \
             tests/cpp/repair_checked_logic tests/cpp/ragged_crc_model tests/cpp/window_map \
-            tests/cpp/ragged_repair_crc_model
+            tests/cpp/ragged_repair_crc_model tests/cpp/ragged_heal_logic
 
 TOOLS    := tools/host_call_rate tools/host_pipeline_sweep tools/host_copy_probe
 
@@ -67,7 +67,7 @@ build/hrs_probe.o: include/hrs_probe.h
 # `make scrub_resources`, `make scrub_crc_resources`, `make heal_erased_resources`,
 # `make heal_erased_crc_resources`, `make repair_resources`, `make ragged_resources`,
 # `make ragged_crc_resources`, `make ragged_repair_resources` (hrs_batch_ragged.hip),
-# `make ragged_repair_crc_resources` (hrs_batch_ragged_crc.hip):
+# `make ragged_repair_crc_resources` (hrs_batch_ragged_crc.hip), `make scrub_ragged_resources`:
 # the compiler's resource report of every kernel of hrs_<name>.hip (the scrub
 # family carries no scratch). Not .PHONY: a phony target takes no pattern rule.
 %_resources: lambdafs_amd/csrc/hrs_%.hip $(HDRS)
@@ -82,7 +82,7 @@ ragged_repair_crc_resources: batch_ragged_crc_resources
 KOBJ     := build/hrs_kernels.o build/hrs_runtime.o build/hrs_batch.o build/hrs_crc.o build/hrs_fused.o build/hrs_decode_crc.o \
             build/hrs_batch_crc.o build/hrs_scrub.o build/hrs_scrub_crc.o build/hrs_heal_erased.o \
             build/hrs_heal_erased_crc.o build/hrs_repair.o build/hrs_ragged.o build/hrs_ragged_crc.o build/hrs_batch_ragged.o \
-            build/hrs_batch_ragged_crc.o
+            build/hrs_batch_ragged_crc.o build/hrs_scrub_ragged.o
 
 $(LIB): $(API_OBJ) $(KOBJ) lambdafs_amd/csrc/libhrs.map
 	$(HIPCC) $(HIPFLAGS) -shared -Wl,--version-script=lambdafs_amd/csrc/libhrs.map -o $@ $(API_OBJ) $(KOBJ) \
@@ -126,6 +126,10 @@ tests/cpp/scrub_logic: tests/cpp/scrub_logic.cpp include/hrs.h $(LIB) $(ORACLE)
 tests/cpp/heal_logic: tests/cpp/heal_logic.cpp include/hrs.h $(LIB) $(ORACLE)
 	g++ -O2 -std=c++17 -Wall -Iinclude -Ioracle -o $@ $< -Llambdafs_amd -lhrs -Loracle -loracle \
 	    -Wl,-rpath,'$$ORIGIN/../../lambdafs_amd' -Wl,-rpath,'$$ORIGIN/../../oracle'
+
+# The ragged heal on the CPU (hrs_heal_ragged_host) vs a model over hrs_compute_error_locations, cells of exactly valid bytes.
+tests/cpp/ragged_heal_logic: tests/cpp/ragged_heal_logic.cpp include/hrs.h $(LIB)
+	g++ -O2 -std=c++17 -Wall -Iinclude -o $@ $< -Llambdafs_amd -lhrs -Wl,-rpath,'$$ORIGIN/../../lambdafs_amd'
 
 # Heal with known erasures on the CPU (hrs_heal_erased_host): uniqueness, capacity, e = 0 vs hrs_heal_host.
 tests/cpp/heal_erased_logic: tests/cpp/heal_erased_logic.cpp include/hrs.h $(LIB) $(ORACLE)
@@ -175,7 +179,7 @@ HSAN     := -Xarch_host -fsanitize=address -Xarch_host -fsanitize=undefined -Xar
             -Xarch_host -fno-omit-frame-pointer
 ASAN_BIN := $(ASAN_DIR)/host_logic $(ASAN_DIR)/jni_harness $(ASAN_DIR)/codec_harness $(ASAN_DIR)/scrub_logic \
             $(ASAN_DIR)/heal_logic $(ASAN_DIR)/heal_erased_logic $(ASAN_DIR)/repair_checked_logic \
-            $(ASAN_DIR)/ragged_crc_model $(ASAN_DIR)/ragged_repair_crc_model
+            $(ASAN_DIR)/ragged_crc_model $(ASAN_DIR)/ragged_repair_crc_model $(ASAN_DIR)/ragged_heal_logic
 ASAN_LOG := profiles/r06/asan
 
 ASAN_API := $(patsubst %,$(ASAN_DIR)/%.o,$(API_SRC))
@@ -202,6 +206,9 @@ $(ASAN_DIR)/scrub_logic: tests/cpp/scrub_logic.cpp $(ASAN_DIR)/libhrs.so $(ASAN_
 
 $(ASAN_DIR)/heal_logic: tests/cpp/heal_logic.cpp $(ASAN_DIR)/libhrs.so $(ASAN_DIR)/liboracle.so
 	$(CLANG)++ $(SAN) -std=c++17 -Iinclude -Ioracle -o $@ $< -L$(ASAN_DIR) -lhrs -loracle $(ASAN_RPATH)
+
+$(ASAN_DIR)/ragged_heal_logic: tests/cpp/ragged_heal_logic.cpp $(ASAN_DIR)/libhrs.so
+	$(CLANG)++ $(SAN) -std=c++17 -Iinclude -o $@ $< -L$(ASAN_DIR) -lhrs $(ASAN_RPATH)
 
 $(ASAN_DIR)/heal_erased_logic: tests/cpp/heal_erased_logic.cpp $(ASAN_DIR)/libhrs.so $(ASAN_DIR)/liboracle.so
 	$(CLANG)++ $(SAN) -std=c++17 -Iinclude -Ioracle -o $@ $< -L$(ASAN_DIR) -lhrs -loracle $(ASAN_RPATH)
@@ -232,6 +239,7 @@ asan: $(ASAN_BIN)
 	  $(ASAN_DIR)/scrub_logic; \
 	  $(ASAN_DIR)/heal_logic; \
 	  $(ASAN_DIR)/heal_erased_logic; \
+	  $(ASAN_DIR)/ragged_heal_logic; \
 	  $(ASAN_DIR)/repair_checked_logic; \
 	  $(ASAN_DIR)/ragged_crc_model; \
 	  $(ASAN_DIR)/ragged_repair_crc_model; \

@@ -508,7 +508,7 @@ hrs_status hrs_encode_batch_host_crc(hrs_codec* codec, uint8_t* stripes, size_t 
  * 3 keep the ragged kernels even then; hrs_set_kernel_mode).
  * Not covered, by design: the synchronous single-stripe host call, the JNI
  * overloads (of the CRC forms below too). Ragged survivors in the repair
- * calls: "ragged repair" below. */
+ * calls: "ragged repair" below; ragged cells at rest: "ragged scrub and heal". */
 
 /* hrs_encode_dev's rows and layout plus valid. Asynchronous on stream; valid
  * is copied before the call returns (through the handle's per-call table
@@ -567,7 +567,8 @@ hrs_status hrs_encode_ragged_batch_host(hrs_codec* codec, uint8_t* stripes, size
  * window size, for tests and A/B runs.
  * Not covered, by design: the synchronous single-stripe host call, the JNI
  * overload. Ragged survivors in the repair calls: "ragged repair" below; the
- * repaired cells' CRCs, which cover no zero fill: "ragged repair + CRC-32". */
+ * repaired cells' CRCs, which cover no zero fill: "ragged repair + CRC-32";
+ * ragged cells at rest: "ragged scrub and heal". */
 
 /* hrs_encode_ragged_dev + the CRC-32 of all k + p cells of every stripe.
  * crc_in / crc_out: DEVICE uint32 [nstripes * (k + p)]. Asynchronous on
@@ -643,7 +644,8 @@ hrs_status hrs_encode_ragged_batch_host_crc(hrs_codec* codec, uint8_t* stripes, 
  * Not covered, by design: patterns that read more than 32 survivors (codes
  * with k > 32, which the plain call serves one stripe at a time: HRS_EINVAL
  * here), the JNI overloads and the single-stripe host call. The CRC forms:
- * "ragged repair + CRC-32" below. */
+ * "ragged repair + CRC-32" below; scrubbing and healing ragged cells: "ragged
+ * scrub and heal". */
 
 /* hrs_decode_batch_dev's layout plus valid. Asynchronous on stream; valid is
  * copied before the call returns (in plan order, through the handle's per-call
@@ -715,7 +717,8 @@ hrs_status hrs_decode_batch_ragged_host(hrs_codec* codec, const uint8_t* stripes
  * ragged kernels even then (hrs_set_kernel_mode).
  * Not covered, by design: the JNI overloads, the single-stripe host call,
  * patterns that read more than 32 survivors, a ragged form of the checked
- * repair. */
+ * repair (its first stage, the scrub and heal over ragged cells, exists:
+ * "ragged scrub and heal" below; its CRC forms and heal-erased do not yet). */
 
 /* hrs_decode_batch_ragged_dev + the CRC-32 of every rebuilt cell over exactly
  * its length. crc_in (nullable) and crc_out are DEVICE arrays of
@@ -828,6 +831,96 @@ hrs_status hrs_heal_batch_host(hrs_codec* codec, uint8_t* stripes, size_t row_st
  * HRS_DEVICE_NONE handles): a plain loop over the columns through the locator
  * the kernels run. report: 4 + n words. len == 0: nothing is touched. */
 hrs_status hrs_heal_host(const hrs_codec* codec, uint8_t* const* rows, size_t len, uint32_t* report);
+
+/* ---- ragged scrub and heal: per-cell lengths, zero tails never read ----
+ * The stripes of a file's tail are encoded from short and empty cells (the
+ * "ragged encode" above: ReadResult.numRead, ParallelStreamReader.java:236-249)
+ * and repaired up to the lost block's real length (the "ragged repair":
+ * Decoder.java:345-369). Their zero tails are stored nowhere. These calls are
+ * hrs_scrub_dev, hrs_heal_dev, hrs_scrub_batch_host, hrs_heal_batch_host and
+ * hrs_heal_host plus one number per cell, so that scrubbing data at rest reads
+ * none of those zeros either:
+ *   - valid is a HOST array of uint32_t[nstripes * n] in hops order, as for the
+ *     ragged repair; valid[s * n + l] is the length of cell l of stripe s, and
+ *     the cell counts as those bytes followed by len - valid zeros.
+ * Column c of stripe s is data[l] = c < valid[s * n + l] ? rows[l][c] : 0, and
+ * computeErrorLocations runs on it exactly as the siblings run it, every quirk
+ * of the reference kept. The report layout is the scrub's, 4 + n words;
+ * HRS_SCRUB_PATCHED is counted by the heal calls only. The calls guarantee:
+ *   - bytes at or beyond a cell's valid never influence a report or a stored
+ *     byte, whatever they hold, and are never written; the storage of the
+ *     whole cell (len bytes) must still be addressable;
+ *   - one rule beyond the siblings', DEMOTION: a virtual zero cannot be
+ *     patched. A column is demoted when the method returns true, blames a
+ *     location l with a nonzero error value, and c >= valid[s * n + l]. A
+ *     demoted column counts as unresolved: word 1, not words 4 + l (words 0
+ *     and 2 count it as usual). Heal stores nothing in a demoted column, also
+ *     not the errors it resolved in live cells of the same column: a
+ *     half-patched column is not a codeword. Scrub and heal apply the same
+ *     rule, so heal's report is still the ragged scrub's report of the stripes
+ *     before the call, plus word 3. A blamed location whose error value is 0
+ *     (the parity_size 8 quirk) demotes nothing.
+ *     A demoted column means: the lengths disagree with the bytes the parity
+ *     was made from (a cell recorded shorter than the data that was encoded);
+ *   - if no column of a batch is demoted, the report equals hrs_scrub_dev's
+ *     over the zero-filled stripes and heal's bytes below valid equal
+ *     hrs_heal_dev's; a batch whose every entry equals len equals the plain
+ *     calls word for word (nothing can be demoted there);
+ *   - the vector kernel loads no 2 KiB window of a cell that lies wholly at or
+ *     beyond the cell's valid, loads and masks the one window that holds the
+ *     boundary, and loads nothing at all for a window at or beyond every
+ *     cell's length of that stripe;
+ *   - the staged host path copies in no byte at or beyond valid and, after a
+ *     heal, copies back only the cells whose word 4 + l is nonzero, and of
+ *     those only the first valid bytes (with HRS_ZEROCOPY=0 no byte at or
+ *     beyond valid is sent to or fetched from the device); runtime-pinned
+ *     batches run as one zero-copy launch in place.
+ * Argument rules, in this order, all before any byte is copied: a NULL handle
+ * is HRS_EINVAL with no message; the sibling's argument rules (code, reports,
+ * rows; heal keeps its NULL-row and equal-rows rule, the host batches their
+ * overlapping-cells rule); a NULL valid is HRS_EINVAL; len == 0 or
+ * nstripes == 0 returns HRS_OK and touches nothing; a valid entry > len is
+ * HRS_EINVAL with the stripe and location named; only then the device is
+ * selected (HRS_EDEVICE for a host-only handle). valid is copied before the
+ * device calls return (through the handle's per-call table slots) and may be
+ * reused at once. Codes as for the scrub: rs, parity_size <= 8, any n <= 255.
+ * Kernels: 16-byte aligned rows and stride take scrub_ragged_kernel<P> /
+ * heal_ragged_kernel<P> over the whole 2 KiB windows (no instantiation uses
+ * scratch); the row tail, unaligned rows or strides and kernel mode 2 take
+ * scrub_ragged_bytewise_kernel<P> / heal_ragged_bytewise_kernel<P>, which load
+ * a location's byte only where the column lies below its length. A batch whose
+ * every entry equals len takes the plain call's route in kernel modes 0 and 1
+ * and hrs_last_kernel names that kernel, so always calling the ragged form
+ * costs one scan of valid; mode 3 keeps the ragged kernels even then
+ * (hrs_set_kernel_mode).
+ * Out of scope, by design: the CRC forms, heal with known erasures, the checked
+ * repair and the JNI overloads over ragged cells. */
+
+/* hrs_scrub_dev's arguments plus valid. Asynchronous on stream. */
+hrs_status hrs_scrub_ragged_dev(hrs_codec* codec, const uint8_t* const* rows, size_t stride, size_t len,
+                                size_t nstripes, const uint32_t* valid, uint32_t* reports, size_t report_stride,
+                                void* stream);
+
+/* hrs_heal_dev's arguments plus valid; the rows are read and, below valid,
+ * written. Asynchronous on stream. */
+hrs_status hrs_heal_ragged_dev(hrs_codec* codec, uint8_t* const* rows, size_t stride, size_t len, size_t nstripes,
+                               const uint32_t* valid, uint32_t* reports, size_t report_stride, void* stream);
+
+/* hrs_scrub_batch_host's layout plus valid (HOST stripes and reports). Synchronous. */
+hrs_status hrs_scrub_ragged_batch_host(hrs_codec* codec, const uint8_t* stripes, size_t row_stride,
+                                       size_t stripe_stride, size_t len, size_t nstripes, const uint32_t* valid,
+                                       uint32_t* reports, size_t report_stride);
+
+/* hrs_heal_batch_host's layout plus valid. Synchronous. */
+hrs_status hrs_heal_ragged_batch_host(hrs_codec* codec, uint8_t* stripes, size_t row_stride, size_t stripe_stride,
+                                      size_t len, size_t nstripes, const uint32_t* valid, uint32_t* reports,
+                                      size_t report_stride);
+
+/* hrs_heal_host plus valid[n]: one stripe of n HOST rows on the CPU (works on
+ * HRS_DEVICE_NONE handles), the kernels' byte-exact reference, demotion
+ * included. */
+hrs_status hrs_heal_ragged_host(const hrs_codec* codec, uint8_t* const* rows, size_t len, const uint32_t* valid,
+                                uint32_t* report);
 
 /* ---- heal with known erasures: repair lost cells and fix survivors ----
  * hrs_decode_batch_dev rebuilds lost cells from survivors it trusts blindly;
@@ -1130,7 +1223,12 @@ hrs_status hrs_repair_checked_host(const hrs_codec* codec, uint8_t* const* rows,
  * take batch_ragged_crc_kernel where the shape has one, 1 and 2 never fuse
  * (ragged repair, crc_ragged_window_kernel over the outputs, fold), 2 with
  * the byte-granular repair; 3 keeps the ragged kernels for an all-full batch
- * too. With nothing lost anywhere only the fold runs. */
+ * too. With nothing lost anywhere only the fold runs.
+ * The ragged scrub and heal calls: 0 and 1 send a batch whose every valid
+ * entry equals len to the plain call's route (hrs_last_kernel names
+ * scrub_kernel / heal_kernel) and every other batch to the ragged kernels; 2
+ * forces scrub_ragged_bytewise_kernel / heal_ragged_bytewise_kernel for every
+ * batch; 3 keeps the ragged kernels for an all-full batch too. */
 hrs_status hrs_set_kernel_mode(hrs_codec* codec, int mode);
 
 #ifdef __cplusplus

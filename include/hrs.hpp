@@ -383,6 +383,47 @@ class HipReedSolomonCode : public HipCode {
     check(hrs_heal_batch_host(h_, stripes, rowStride, stripeStride, len, nstripes, reports, reportStride), h_);
   }
 
+  // The ragged scrub and heal (hrs_scrub_ragged_dev, hrs_heal_ragged_dev and
+  // their host batches): scrubDev / healDev over cells of which only the
+  // leading valid[s * n + l] bytes (HOST words, hops order) hold data; the
+  // zeros behind them are never read, and a column that could only be fixed by
+  // patching such a zero counts as unresolved (include/hrs.h, "demotion").
+  void scrubRaggedDev(const std::vector<const uint8_t*>& rows, size_t stride, size_t len, size_t nstripes,
+                      const uint32_t* valid, uint32_t* reports, size_t reportStride, void* stream = nullptr) {
+    if (static_cast<int>(rows.size()) != stripeSize() + paritySize())
+      throw std::invalid_argument("scrubRaggedDev: row count does not match the codec");
+    check(hrs_scrub_ragged_dev(h_, rows.data(), stride, len, nstripes, valid, reports, reportStride, stream), h_);
+  }
+
+  void healRaggedDev(const std::vector<uint8_t*>& rows, size_t stride, size_t len, size_t nstripes,
+                     const uint32_t* valid, uint32_t* reports, size_t reportStride, void* stream = nullptr) {
+    if (static_cast<int>(rows.size()) != stripeSize() + paritySize())
+      throw std::invalid_argument("healRaggedDev: row count does not match the codec");
+    check(hrs_heal_ragged_dev(h_, rows.data(), stride, len, nstripes, valid, reports, reportStride, stream), h_);
+  }
+
+  void scrubRaggedBatchHost(const uint8_t* stripes, size_t rowStride, size_t stripeStride, size_t len, size_t nstripes,
+                            const uint32_t* valid, uint32_t* reports, size_t reportStride) {
+    check(hrs_scrub_ragged_batch_host(h_, stripes, rowStride, stripeStride, len, nstripes, valid, reports,
+                                      reportStride),
+          h_);
+  }
+
+  void healRaggedBatchHost(uint8_t* stripes, size_t rowStride, size_t stripeStride, size_t len, size_t nstripes,
+                           const uint32_t* valid, uint32_t* reports, size_t reportStride) {
+    check(hrs_heal_ragged_batch_host(h_, stripes, rowStride, stripeStride, len, nstripes, valid, reports,
+                                     reportStride),
+          h_);
+  }
+
+  // One stripe of n host rows on the CPU (hrs_heal_ragged_host; host-only
+  // handles too): valid[n], report 4 + n words.
+  void healRaggedHost(const std::vector<uint8_t*>& rows, size_t len, const uint32_t* valid, uint32_t* report) {
+    if (static_cast<int>(rows.size()) != stripeSize() + paritySize())
+      throw std::invalid_argument("healRaggedHost: row count does not match the codec");
+    check(hrs_heal_ragged_host(h_, rows.data(), len, valid, report), h_);
+  }
+
   // scrubDev / healDev plus the CRC-32 of every cell from the same read
   // (hrs_scrub_crc_dev / hrs_heal_crc_dev): crcOut[s * n + l] in HOPS order
   // (parity first, the order of rows), continued from crcIn (nullptr: fresh);

@@ -54,6 +54,8 @@ EXPORTS = (
     "hrs_encode_ragged_crc_dev", "hrs_encode_ragged_batch_host_crc",
     "hrs_decode_batch_ragged_dev", "hrs_decode_batch_ragged_host",
     "hrs_decode_batch_ragged_crc_dev", "hrs_decode_batch_ragged_host_crc",
+    "hrs_scrub_ragged_dev", "hrs_heal_ragged_dev", "hrs_scrub_ragged_batch_host", "hrs_heal_ragged_batch_host",
+    "hrs_heal_ragged_host",
 )
 # include/hrs_probe.h, exported by libhrs_probe.so
 PROBE_EXPORTS = ("hrs_probe_stream", "hrs_probe_rows")
@@ -161,6 +163,11 @@ def lib():
         "hrs_decode_batch_ragged_host": ([P, P, S, S, P, I, P, S, S, S, S, P], I),
         "hrs_decode_batch_ragged_crc_dev": ([P, P, S, S, P, I, P, S, S, S, S, P, P, P, P], I),
         "hrs_decode_batch_ragged_host_crc": ([P, P, S, S, P, I, P, S, S, S, S, P, P, P], I),
+        "hrs_scrub_ragged_dev": ([P, PP, S, S, S, P, P, S, P], I),
+        "hrs_heal_ragged_dev": ([P, PP, S, S, S, P, P, S, P], I),
+        "hrs_scrub_ragged_batch_host": ([P, P, S, S, S, S, P, P, S], I),
+        "hrs_heal_ragged_batch_host": ([P, P, S, S, S, S, P, P, S], I),
+        "hrs_heal_ragged_host": ([P, PP, S, P, P], I),
     }
     for name, (args, res) in sigs.items():
         if os.environ.get("HRS_LIB") and not hasattr(L, name):

@@ -350,6 +350,36 @@ hrs_status run_scrub_crc(hrs_codec* c, const uint8_t* const* rows, size_t stride
 // kernel mode 0 or 3.
 bool scrub_crc_one_pass(const hrs_codec* c, const uint8_t* const* rows, size_t stride, size_t len);
 
+// ---- ragged scrub and heal (hrs_scrub_api.cpp; kernels: hrs_scrub_ragged.hip)
+// The cells of a host batch must not overlap (hrs_scrub_batch_host's rule,
+// include/hrs.h): HRS_EINVAL with the strides named. len, nstripes > 0.
+hrs_status scrub_cells_apart_ok(hrs_codec* c, size_t row_stride, size_t stripe_stride, size_t len, size_t nstripes);
+// The argument rules of the ragged scrub / heal entry points (include/hrs.h),
+// before the device is selected: scrub_args_ok with `flags`, for a batch image
+// (kScrubImage) with bytes in it scrub_cells_apart_ok, valid not NULL, the
+// empty batch (*empty = true: return HRS_OK and touch nothing), every one of
+// the nstripes * n HOST words of `valid` <= len (the stripe and location
+// named). *all_full: every word equals len.
+hrs_status scrub_ragged_args_ok(hrs_codec* c, const void* cells, const uint32_t* reports, size_t report_stride,
+                                size_t len, size_t nstripes, unsigned flags, size_t row_stride, size_t stripe_stride,
+                                const uint32_t* valid, bool* empty, bool* all_full);
+// Whether a ragged scrub / heal batch takes the plain route: every cell full,
+// in kernel modes 0 and 1 (2 and 3 keep the ragged kernels).
+inline bool scrub_ragged_takes_plain(const hrs_codec* c, bool all_full) {
+  return all_full && (c->kernel_mode == 0 || c->kernel_mode == 1);
+}
+// The device length table of a ragged scrub / heal (hrs_scrub_ragged.hpp:
+// n + 1 words per stripe) from valid[nstripes * n], through a batch slot and up
+// to the device on s. The caller calls slot_used after its launches.
+hrs_status scrub_ragged_table(hrs_codec* c, const uint32_t* valid, size_t nstripes, hipStream_t s,
+                              hrs_codec::BatchSlot** slot, const uint32_t** dlens);
+// run_scrub over cells that read as zero from their length on: dlens is the
+// device table at the range's first stripe. The ragged window kernel over the
+// whole 2 KiB windows of aligned rows, the byte-granular ragged kernel over the
+// rest (everything in kernel mode 2).
+hrs_status run_scrub_ragged(hrs_codec* c, const uint8_t* const* rows, size_t stride, size_t len, size_t nstripes,
+                            const uint32_t* dlens, uint32_t* reports, size_t report_stride, hipStream_t s, bool heal);
+
 // ---- heal with known erasures (hrs_scrub_api.cpp)
 // The erased set of one stripe: entries up to the first negative one (or
 // `cap`), sorted ascending into `key`. HRS_EINVAL for a location outside

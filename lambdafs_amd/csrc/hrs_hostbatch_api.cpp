@@ -1,5 +1,6 @@
 // Host-memory batches (hrs_decode_batch_host, hrs_encode_batch_host, the
 // scrub / heal / heal-erased host batches, each with its block-CRC-32 form,
+// the ragged scrub and heal hrs_scrub_ragged_batch_host / hrs_heal_ragged_batch_host,
 // the ragged encodes hrs_encode_ragged_batch_host[_crc] and the ragged repairs
 // hrs_decode_batch_ragged_host[_crc]):
 // memory classification and the zero-copy knobs, the chunk pipeline (chunks of
@@ -23,6 +24,7 @@
 #include "hrs_host.hpp"
 #include "hrs_internal.hpp"
 #include "hrs_launch.hpp"
+#include "hrs_scrub_ragged.hpp"
 
 namespace hrs::api {
 
@@ -252,6 +254,8 @@ struct HostJob {
   std::function<hrs_status(const Chunk&)> compute;
   std::function<int(size_t)> writes;
   std::function<hrs_status(size_t, size_t, std::vector<DirtyCell>&)> dirty;
+  // (optional; the ragged calls) in_bytes(s, l): the leading bytes of cell l of
+  // stripe s that are copied in, and copied back when the cell is dirty.
   std::function<size_t(size_t, int)> in_bytes;
   // (optional; the ragged repair) out_bytes(s, t): the leading bytes of output
   // t of stripe s that go back to the caller; 0 skips the copy.
@@ -328,9 +332,11 @@ hrs_status host_batch(hrs_codec* c, const HostJob& job) {
       for (const DirtyCell& d : cells) {
         uint8_t* dst = const_cast<uint8_t*>(hin) + (pend[sl].s0 + d.i) * job.in_stripe + d.l * job.in_row;
         const size_t at = d.i * img_stripe + d.l * dpitch;
+        const size_t nb = ragged ? job.in_bytes(pend[sl].s0 + d.i, d.l) : len;  // a ragged cell: its leading bytes
+        if (nb == 0) continue;
         if (zc) {
-          jobs.push_back({dst, h.pin + at, len});
-        } else if ((e = hipMemcpy(dst, h.dev + at, len, hipMemcpyDeviceToHost)) != hipSuccess) {
+          jobs.push_back({dst, h.pin + at, nb});
+        } else if ((e = hipMemcpy(dst, h.dev + at, nb, hipMemcpyDeviceToHost)) != hipSuccess) {
           return hip_fail(c, e, "D2H of a healed cell");
         }
       }
@@ -819,10 +825,20 @@ hrs_status encode_ragged_batch_host_entry(hrs_codec* c, uint8_t* stripes, size_t
 // survivor rows (the slot image keeps stale bytes at erased rows; the kernels
 // write every byte of them) and copies back the erased cells plus the cells
 // with a nonzero count in word 4 + l.
+// valid != NULL (hrs_scrub_ragged_batch_host, hrs_heal_ragged_batch_host; no
+// CRCs, no erasures): cell l of stripe s holds valid[s * n + l] leading bytes.
+// The length table goes up once through a batch slot, on the one launch's
+// stream (pinned) or on slot 0's with the other slot streams waiting for it
+// (staged); run_scrub_ragged takes each chunk's slice of it. A staged chunk
+// copies in only those bytes of each cell and copies back only those of a
+// dirty one; what the slot image keeps behind them the ragged kernels mask.
 hrs_status scrub_batch_host_job(hrs_codec* c, const uint8_t* stripes, size_t row_stride, size_t stripe_stride,
                                 size_t len, size_t nstripes, uint32_t* reports, size_t report_stride, bool heal,
-                                HostCrcs& crcs, const ErasedSets* es) {
+                                HostCrcs& crcs, const ErasedSets* es, const uint32_t* valid = nullptr) {
   const int n = c->n;
+  const size_t lwords = hrs::scrub_ragged_words(n);
+  hrs_codec::BatchSlot* lslot = nullptr;
+  const uint32_t* dlens = nullptr;
   hrs_status st = crcs.on_device();
   if (st != HRS_OK) return st;
   const size_t nwords = static_cast<size_t>(hrs::kScrubHead + n);
@@ -835,6 +851,7 @@ hrs_status scrub_batch_host_job(hrs_codec* c, const uint8_t* stripes, size_t row
     for (int l = 0; l < n; ++l) rows[l] = img + static_cast<size_t>(l) * pitch;
     const uint8_t* const* r = rows.data();
     uint32_t* rep = drep + s0 * nwords;
+    if (valid) return run_scrub_ragged(c, r, stride, len, ns, dlens + s0 * lwords, rep, nwords, hs, heal);
     if (es) {
       uint8_t* const* w = reinterpret_cast<uint8_t* const*>(const_cast<uint8_t**>(r));
       if (!crcs) return run_heal_erased(c, w, stride, len, ns, es->pats, es->pat.data() + s0, rep, nwords, hs);
@@ -847,8 +864,25 @@ hrs_status scrub_batch_host_job(hrs_codec* c, const uint8_t* stripes, size_t row
   uint8_t* zs = nullptr;
   if (zero_copy_on() && host_device_ptr(stripes, batch_span(nstripes, stripe_stride, n, row_stride, len), &zs)) {
     // runtime-pinned: one launch reads the caller's stripes across the host link
-    st = zero_copy_call(c, [&](hipStream_t hs) { return scrub(hs, 0, nstripes, zs, row_stride, stripe_stride); });
+    st = zero_copy_call(c, [&](hipStream_t hs) {
+      if (valid && (st = scrub_ragged_table(c, valid, nstripes, hs, &lslot, &dlens)) != HRS_OK) return st;
+      st = scrub(hs, 0, nstripes, zs, row_stride, stripe_stride);
+      if (lslot) slot_used(lslot, hs);
+      return st;
+    });
   } else {
+    hipStream_t first = nullptr;
+    if (valid) {
+      if ((st = hbatch_slot(c, 0, 0, 0)) != HRS_OK) return st;
+      first = c->hbatch[0].stream;
+      if ((st = scrub_ragged_table(c, valid, nstripes, first, &lslot, &dlens)) != HRS_OK) return st;
+      slot_used(lslot, first);
+      for (int i = 1; i < hrs::kHostBatchSlots; ++i) {
+        if ((st = hbatch_slot(c, i, 0, 0)) != HRS_OK) return st;
+        const hipError_t e = hipStreamWaitEvent(c->hbatch[i].stream, lslot->done, 0);
+        if (e != hipSuccess) return hip_fail(c, e, "hipStreamWaitEvent");
+      }
+    }
     const std::vector<RowRun> all_rows{{0, n}};
     std::vector<std::vector<RowRun>> survivor_runs(es ? es->keys.size() : 0);  // per pattern
     for (size_t id = 0; id < survivor_runs.size(); ++id) {
@@ -862,6 +896,7 @@ hrs_status scrub_batch_host_job(hrs_codec* c, const uint8_t* stripes, size_t row
     hj.reads = [&](size_t s) -> const std::vector<RowRun>& { return es ? survivor_runs[es->pat[s]] : all_rows; };
     hj.writes = [](size_t) { return 0; };
     hj.compute = [&](const Chunk& k) { return scrub(k.hs, k.s0, k.ns, k.img, k.pitch, k.img_stripe); };
+    if (valid) hj.in_bytes = [&](size_t s, int l) { return static_cast<size_t>(valid[s * static_cast<size_t>(n) + l]); };
     std::vector<uint32_t> chunk_rep;
     if (heal)
       hj.dirty = [&](size_t s0, size_t ns, std::vector<DirtyCell>& cells) -> hrs_status {
@@ -878,6 +913,7 @@ hrs_status scrub_batch_host_job(hrs_codec* c, const uint8_t* stripes, size_t row
         return HRS_OK;
       };
     st = host_batch(c, hj);
+    if (lslot) slot_used(lslot, first);  // the table's slot is reused only after this job's kernels
   }
   if (st != HRS_OK) return st;
   std::vector<uint32_t> host(nstripes * nwords);
@@ -904,15 +940,8 @@ hrs_status scrub_batch_host_entry(hrs_codec* c, const uint8_t* stripes, size_t r
   if (with_erased && (st = erased_sets(c, erased, max_erased, nstripes, es)) != HRS_OK) return st;
   if (nstripes == 0 || len == 0) return HRS_OK;
   // A read-only pass over a mis-strided batch would report "clean" or "bad"
-  // with no error: the cells must not overlap. Rows of a stripe packed inside
-  // the stripe stride, or stripes of a row packed inside the row stride.
-  const size_t rows_span = static_cast<size_t>(c->n - 1) * row_stride + len;
-  const size_t stripes_span = (nstripes - 1) * stripe_stride + len;
-  const bool stripes_apart =
-      nstripes == 1 || (stripe_stride >= len && (stripe_stride >= rows_span || row_stride >= stripes_span));
-  if (row_stride < len || !stripes_apart)
-    return fail(c, HRS_EINVAL, "cells overlap: row_stride %zu, stripe_stride %zu, len %zu, %d rows, %zu stripes",
-                row_stride, stripe_stride, len, c->n, nstripes);
+  // with no error: the cells must not overlap.
+  if ((st = scrub_cells_apart_ok(c, row_stride, stripe_stride, len, nstripes)) != HRS_OK) return st;
   const size_t ncrc = nstripes * static_cast<size_t>(c->n);
   if (with_crc && (st = crc_args_ok(c, crc_in, crc_out, ncrc)) != HRS_OK) return st;
   // max_erased == 0: nothing can be erased, the heal itself
@@ -921,6 +950,26 @@ hrs_status scrub_batch_host_entry(hrs_codec* c, const uint8_t* stripes, size_t r
                          HostCrcs{c, ncrc, crc_in, with_crc ? crc_out : nullptr}, true, [&](HostCrcs& crcs) {
                            return scrub_batch_host_job(c, stripes, row_stride, stripe_stride, len, nstripes, reports,
                                                        report_stride, heal, crcs, sets);
+                         });
+}
+
+// hrs_scrub_ragged_batch_host and hrs_heal_ragged_batch_host: the rules of
+// scrub_ragged_args_ok (the sibling's gate and cell-overlap rule, then valid),
+// then the sibling's job with the lengths; an all-full batch in kernel modes 0
+// and 1 is the sibling's job.
+hrs_status scrub_ragged_batch_host_entry(hrs_codec* c, const uint8_t* stripes, size_t row_stride, size_t stripe_stride,
+                                         size_t len, size_t nstripes, const uint32_t* valid, uint32_t* reports,
+                                         size_t report_stride, bool heal) {
+  bool empty = false, all_full = false;
+  const hrs_status st = scrub_ragged_args_ok(c, stripes, reports, report_stride, len, nstripes,
+                                             kScrubWithReports | kScrubImage, row_stride, stripe_stride, valid, &empty,
+                                             &all_full);
+  if (st != HRS_OK || empty) return st;
+  const uint32_t* lengths = scrub_ragged_takes_plain(c, all_full) ? nullptr : valid;
+  return host_batch_call(c, stripes, batch_span(nstripes, stripe_stride, c->n, row_stride, len), nullptr, 0,
+                         HostCrcs{c, 0, nullptr, nullptr}, true, [&](HostCrcs& crcs) {
+                           return scrub_batch_host_job(c, stripes, row_stride, stripe_stride, len, nstripes, reports,
+                                                       report_stride, heal, crcs, nullptr, lengths);
                          });
 }
 
@@ -998,6 +1047,20 @@ hrs_status hrs_scrub_batch_host(hrs_codec* c, const uint8_t* stripes, size_t row
 hrs_status hrs_heal_batch_host(hrs_codec* c, uint8_t* stripes, size_t row_stride, size_t stripe_stride, size_t len,
                                size_t nstripes, uint32_t* reports, size_t report_stride) {
   return scrub_batch_host_entry(c, stripes, row_stride, stripe_stride, len, nstripes, reports, report_stride, true);
+}
+
+hrs_status hrs_scrub_ragged_batch_host(hrs_codec* c, const uint8_t* stripes, size_t row_stride, size_t stripe_stride,
+                                       size_t len, size_t nstripes, const uint32_t* valid, uint32_t* reports,
+                                       size_t report_stride) {
+  return scrub_ragged_batch_host_entry(c, stripes, row_stride, stripe_stride, len, nstripes, valid, reports,
+                                       report_stride, false);
+}
+
+hrs_status hrs_heal_ragged_batch_host(hrs_codec* c, uint8_t* stripes, size_t row_stride, size_t stripe_stride,
+                                      size_t len, size_t nstripes, const uint32_t* valid, uint32_t* reports,
+                                      size_t report_stride) {
+  return scrub_ragged_batch_host_entry(c, stripes, row_stride, stripe_stride, len, nstripes, valid, reports,
+                                       report_stride, true);
 }
 
 hrs_status hrs_scrub_batch_host_crc(hrs_codec* c, const uint8_t* stripes, size_t row_stride, size_t stripe_stride,

@@ -2,7 +2,8 @@
 // computeErrorLocations on the host (hrs_compute_error_locations, host-only
 // handles included), the device-resident batches (hrs_scrub_dev, hrs_heal_dev,
 // hrs_scrub_crc_dev, hrs_heal_crc_dev with the cells' CRC-32s from the same
-// pass, and hrs_heal_erased_dev / hrs_heal_erased_crc_dev with their erasure
+// pass, hrs_scrub_ragged_dev, hrs_heal_ragged_dev over cells with per-cell
+// lengths (their gate scrub_ragged_args_ok, hrs_heal_ragged_host on the CPU), and hrs_heal_erased_dev / hrs_heal_erased_crc_dev with their erasure
 // patterns: validated, de-duplicated, with the constants the kernels of
 // hrs_heal_erased.hip and hrs_heal_erased_crc.hip multiply by) and one stripe
 // healed on the CPU (hrs_heal_host, hrs_heal_erased_host), the kernels'
@@ -32,6 +33,7 @@
 #include "hrs_launch.hpp"
 #include "hrs_locator.hpp"
 #include "hrs_repair_rule.hpp"
+#include "hrs_scrub_ragged.hpp"
 
 namespace hrs::api {
 
@@ -146,6 +148,70 @@ hrs_status run_scrub(hrs_codec* c, const uint8_t* const* rows, size_t stride, si
       [&] { return heal ? hrs::launch_heal_bytewise(a, s) : hrs::launch_scrub_bytewise(a, s); });
 }
 
+// ---- ragged scrub and heal
+
+hrs_status scrub_cells_apart_ok(hrs_codec* c, size_t row_stride, size_t stripe_stride, size_t len, size_t nstripes) {
+  // Rows of a stripe packed inside the stripe stride, or stripes of a row packed inside the row stride.
+  const size_t rows_span = static_cast<size_t>(c->n - 1) * row_stride + len;
+  const size_t stripes_span = (nstripes - 1) * stripe_stride + len;
+  const bool stripes_apart =
+      nstripes == 1 || (stripe_stride >= len && (stripe_stride >= rows_span || row_stride >= stripes_span));
+  if (row_stride < len || !stripes_apart)
+    return fail(c, HRS_EINVAL, "cells overlap: row_stride %zu, stripe_stride %zu, len %zu, %d rows, %zu stripes",
+                row_stride, stripe_stride, len, c->n, nstripes);
+  return HRS_OK;
+}
+
+hrs_status scrub_ragged_args_ok(hrs_codec* c, const void* cells, const uint32_t* reports, size_t report_stride,
+                                size_t len, size_t nstripes, unsigned flags, size_t row_stride, size_t stripe_stride,
+                                const uint32_t* valid, bool* empty, bool* all_full) {
+  *empty = *all_full = false;
+  hrs_status st = scrub_args_ok(c, cells, reports, report_stride, len, nstripes, flags);
+  if (st != HRS_OK) return st;
+  const bool none = len == 0 || nstripes == 0;
+  if ((flags & kScrubImage) && !none && (st = scrub_cells_apart_ok(c, row_stride, stripe_stride, len, nstripes)) != HRS_OK)
+    return st;
+  if (!valid) return fail(c, HRS_EINVAL, "valid is NULL");
+  if (none) {
+    *empty = true;
+    return HRS_OK;
+  }
+  const size_t n = static_cast<size_t>(c->n);
+  bool full = true;
+  for (size_t s = 0; s < nstripes; ++s)
+    for (size_t l = 0; l < n; ++l) {
+      const uint32_t v = valid[s * n + l];
+      if (v > len) return fail(c, HRS_EINVAL, "stripe %zu location %zu: valid %u exceeds len %zu", s, l, v, len);
+      full &= v == len;
+    }
+  *all_full = full;
+  return HRS_OK;
+}
+
+hrs_status scrub_ragged_table(hrs_codec* c, const uint32_t* valid, size_t nstripes, hipStream_t s,
+                              hrs_codec::BatchSlot** slot, const uint32_t** dlens) {
+  const size_t n = static_cast<size_t>(c->n), words = hrs::scrub_ragged_words(c->n);
+  std::vector<uint32_t> table(nstripes * words);
+  for (size_t i = 0; i < nstripes; ++i) {
+    uint32_t most = 0;
+    for (size_t l = 0; l < n; ++l) most = std::max(most, table[i * words + l] = valid[i * n + l]);
+    table[i * words + n] = most;
+  }
+  const hrs_status st = upload(c, table.data(), table.size() * sizeof(uint32_t), table.data(), 0, s, slot);
+  if (st != HRS_OK) return st;
+  *dlens = reinterpret_cast<const uint32_t*>((*slot)->dev);
+  return HRS_OK;
+}
+
+hrs_status run_scrub_ragged(hrs_codec* c, const uint8_t* const* rows, size_t stride, size_t len, size_t nstripes,
+                            const uint32_t* dlens, uint32_t* reports, size_t report_stride, hipStream_t s, bool heal) {
+  hrs::ScrubRaggedArgs a{};
+  a.lens = dlens;
+  return run_windows_tail(
+      c, a.s, rows, stride, len, nstripes, reports, report_stride, s, heal ? "ragged heal" : "ragged scrub",
+      [&] { return hrs::launch_scrub_ragged(a, heal, s); }, [&] { return hrs::launch_scrub_ragged_bytewise(a, heal, s); });
+}
+
 namespace {
 
 // One stripe on the CPU: the column loop of hrs_heal_host (an empty pattern,
@@ -153,14 +219,20 @@ namespace {
 // cells count as zero and are rebuilt, locate_errata()). write = false (empty
 // pattern only) is the scrub: the same report with nothing stored and word 3
 // left at 0, pass 1 of hrs_repair_checked_host.
-template <int P>
-void heal_stripe(int n, uint8_t* const* rows, size_t len, const hrs::ErasePattern& pt, uint32_t* rep, bool write) {
+// Ragged (hrs_heal_ragged_host; empty pattern only): cell l counts as its
+// valid[l] leading bytes followed by zeros, and a column resolved by blaming,
+// with a nonzero error value, a cell it lies at or beyond is demoted to
+// unresolved (include/hrs.h). Without it the loop is the code it always was.
+template <int P, bool Ragged = false>
+void heal_stripe(int n, uint8_t* const* rows, size_t len, const hrs::ErasePattern& pt, uint32_t* rep, bool write,
+                 const uint32_t* valid = nullptr) {
   const hrs::locator::Field& f = kHostField;
   const int e = pt.e;
   for (size_t col = 0; col < len; ++col) {
     uint8_t s[P] = {};
     for (int l = n - 1; l >= 0; --l) {
-      const bool gone = (pt.mask[l >> 5] >> (l & 31)) & 1u;
+      bool gone = (pt.mask[l >> 5] >> (l & 31)) & 1u;
+      if constexpr (Ragged) gone |= col >= valid[l];
       hrs::locator::horner_step<P>(f, s, gone ? uint8_t{0} : rows[l][col]);
     }
     int nloc = 0, state;
@@ -170,6 +242,9 @@ void heal_stripe(int n, uint8_t* const* rows, size_t len, const hrs::ErasePatter
       for (int i = 0; i < P; ++i) nz |= s[i];
       if (nz == 0) continue;
       state = hrs::locator::locate(f, n, P, s, &nloc, loc, u) ? hrs::locator::kResolved : hrs::locator::kUnresolved;
+      if constexpr (Ragged)
+        for (int j = 0; j < nloc && state == hrs::locator::kResolved; ++j)
+          if (u[j] != 0 && col >= valid[loc[j]]) state = hrs::locator::kUnresolved;  // a patch of a virtual zero
     } else {
       state = hrs::locator::locate_errata<P>(f, n, s, e, pt.loc, pt.gamma, &nloc, loc, u, v);
       for (int m = 0; m < e; ++m) rows[pt.loc[m]][col] = v[m];
@@ -191,11 +266,15 @@ void heal_stripe(int n, uint8_t* const* rows, size_t len, const hrs::ErasePatter
 }
 
 // hrs_heal_host and hrs_heal_erased_host after their argument checks.
+// valid (hrs_heal_ragged_host, empty pattern): the cells' lengths.
 hrs_status heal_host(hrs_codec* c, uint8_t* const* rows, size_t len, const hrs::ErasePattern& pt, uint32_t* report,
-                     bool write = true) {
+                     bool write = true, const uint32_t* valid = nullptr) {
   if (len == 0) return HRS_OK;
   for (int e = 0; e < HRS_SCRUB_HEAD + c->n; ++e) report[e] = e == HRS_SCRUB_FIRST_BAD ? HRS_SCRUB_NONE : 0u;
-  (void)hrs::dispatch_p<1, 8>(c->p, [&](auto P) { heal_stripe<P>(c->n, rows, len, pt, report, write); });
+  (void)hrs::dispatch_p<1, 8>(c->p, [&](auto P) {
+    if (valid) heal_stripe<P, true>(c->n, rows, len, pt, report, write, valid);
+    else heal_stripe<P>(c->n, rows, len, pt, report, write);
+  });
   return HRS_OK;
 }
 
@@ -238,6 +317,30 @@ hrs_status scrub_dev_entry(hrs_codec* c, const uint8_t* const* rows, size_t stri
   DeviceGuard g(c->device);
   if (!g.ok) return fail(c, HRS_EDEVICE, "cannot select HIP device %d", c->device);
   return run_scrub(c, rows, stride, len, nstripes, reports, report_stride, static_cast<hipStream_t>(stream), heal);
+}
+
+// hrs_scrub_ragged_dev and hrs_heal_ragged_dev: the rules of scrub_ragged_args_ok,
+// the device, then the sibling's route for an all-full batch in kernel modes 0
+// and 1, else the length table through a batch slot and the ragged kernels.
+hrs_status scrub_ragged_dev_entry(hrs_codec* c, const uint8_t* const* rows, size_t stride, size_t len, size_t nstripes,
+                                  const uint32_t* valid, uint32_t* reports, size_t report_stride, void* stream,
+                                  bool heal) {
+  bool empty = false, all_full = false;
+  hrs_status st = scrub_ragged_args_ok(c, rows, reports, report_stride, len, nstripes,
+                                       kScrubWithReports | (heal ? kScrubRowsWritten : 0u), 0, 0, valid, &empty,
+                                       &all_full);
+  if (st != HRS_OK || empty) return st;
+  DeviceGuard g(c->device);
+  if (!g.ok) return fail(c, HRS_EDEVICE, "cannot select HIP device %d", c->device);
+  hipStream_t s = static_cast<hipStream_t>(stream);
+  if (scrub_ragged_takes_plain(c, all_full))
+    return run_scrub(c, rows, stride, len, nstripes, reports, report_stride, s, heal);
+  hrs_codec::BatchSlot* sl = nullptr;
+  const uint32_t* dlens = nullptr;
+  if ((st = scrub_ragged_table(c, valid, nstripes, s, &sl, &dlens)) != HRS_OK) return st;
+  st = run_scrub_ragged(c, rows, stride, len, nstripes, dlens, reports, report_stride, s, heal);
+  slot_used(sl, s);
+  return st;
 }
 
 // hrs_scrub_crc_dev and hrs_heal_crc_dev: the sibling call's argument rules, then the CRC arrays'.
@@ -532,6 +635,26 @@ hrs_status hrs_scrub_dev(hrs_codec* c, const uint8_t* const* rows, size_t stride
 hrs_status hrs_heal_dev(hrs_codec* c, uint8_t* const* rows, size_t stride, size_t len, size_t nstripes,
                         uint32_t* reports, size_t report_stride, void* stream) {
   return scrub_dev_entry(c, rows, stride, len, nstripes, reports, report_stride, stream, true);
+}
+
+hrs_status hrs_scrub_ragged_dev(hrs_codec* c, const uint8_t* const* rows, size_t stride, size_t len, size_t nstripes,
+                                const uint32_t* valid, uint32_t* reports, size_t report_stride, void* stream) {
+  return scrub_ragged_dev_entry(c, rows, stride, len, nstripes, valid, reports, report_stride, stream, false);
+}
+
+hrs_status hrs_heal_ragged_dev(hrs_codec* c, uint8_t* const* rows, size_t stride, size_t len, size_t nstripes,
+                               const uint32_t* valid, uint32_t* reports, size_t report_stride, void* stream) {
+  return scrub_ragged_dev_entry(c, rows, stride, len, nstripes, valid, reports, report_stride, stream, true);
+}
+
+hrs_status hrs_heal_ragged_host(const hrs_codec* cc, uint8_t* const* rows, size_t len, const uint32_t* valid,
+                                uint32_t* report) {
+  auto* c = const_cast<hrs_codec*>(cc);
+  bool empty = false, all_full = false;
+  const hrs_status st =
+      scrub_ragged_args_ok(c, rows, report, 0, len, 1, kScrubRowsWritten, 0, 0, valid, &empty, &all_full);
+  if (st != HRS_OK || empty) return st;
+  return heal_host(c, rows, len, hrs::ErasePattern{}, report, true, valid);
 }
 
 hrs_status hrs_scrub_crc_dev(hrs_codec* c, const uint8_t* const* rows, size_t stride, size_t len, size_t nstripes,

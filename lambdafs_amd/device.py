@@ -559,12 +559,16 @@ def _erased_array(erased, S, what="erased"):
     return arr
 
 
-def _scrub(code, batch, op, erased=None, crcs=None):
+def _scrub(code, batch, op, erased=None, crcs=None, valid=None):
     """hrs_<op>_dev or hrs_<op>_crc_dev over _code_stripes' or _code_rows'
-    tuple; op is "scrub", "heal" or, with `erased`, "heal_erased". Returns
-    the reports, with CRCs (reports, crcs)."""
+    tuple; op is "scrub", "heal" or, with `erased`, "heal_erased"; with `valid`
+    (the cells' lengths, [S, n]) "scrub_ragged" or "heal_ragged". Returns the
+    reports, with CRCs (reports, crcs)."""
     rows, stride, L, S, ref = batch
     args = [code._handle(), rows, stride, L, S]
+    if valid is not None:
+        v = _ragged_valid(code, valid, S, code.stripeSize() + code.paritySize())
+        args.append(v.ctypes.data)
     if erased is not None:
         arr = _erased_array(erased, S)
         args += [arr.ctypes.data, arr.shape[1]]
@@ -580,10 +584,13 @@ def _scrub(code, batch, op, erased=None, crcs=None):
     return reports, crc
 
 
-def _scrub_batch_host(code, stripes, op, erased=None, crcs=None):
-    """hrs_<op>_batch_host or hrs_<op>_batch_host_crc; op and the result as for _scrub."""
-    sp, row_stride, stripe_stride, L, S = _host_batch(code, stripes, writable=op != "scrub")
+def _scrub_batch_host(code, stripes, op, erased=None, crcs=None, valid=None):
+    """hrs_<op>_batch_host or hrs_<op>_batch_host_crc; op, valid and the result as for _scrub."""
+    sp, row_stride, stripe_stride, L, S = _host_batch(code, stripes, writable=not op.startswith("scrub"))
     args = [code._handle(), sp, row_stride, stripe_stride, L, S]
+    if valid is not None:
+        v = _ragged_valid(code, valid, S, code.stripeSize() + code.paritySize())
+        args.append(v.ctypes.data)
     if erased is not None:
         arr = _erased_array(erased, S)
         args += [arr.ctypes.data, arr.shape[1]]
@@ -650,6 +657,47 @@ def heal_host(code, rows):
     report[SCRUB_FIRST_BAD] = SCRUB_NONE
     code._check(_lib.lib().hrs_heal_host(code._handle(), _lib.ptr_array([r.ctypes.data for r in rows]), L,
                                          report.ctypes.data))
+    return report
+
+
+def scrub_stripes_ragged(code, stripes, valid):
+    """scrub_stripes over cells of which only the leading valid[s, l] bytes
+    hold data (hrs_scrub_ragged_dev): cell l of stripe s counts as those bytes
+    followed by zeros, which are never read. valid: anything convertible to a
+    uint32 [S, n] array in hops order, free for reuse on return. A column that
+    only a patch of such a zero would resolve counts as unresolved."""
+    return _scrub(code, _code_stripes(code, stripes), "scrub_ragged", valid=valid)
+
+
+def heal_stripes_ragged(code, stripes, valid):
+    """heal_stripes under scrub_stripes_ragged's lengths (hrs_heal_ragged_dev):
+    nothing at or beyond a cell's valid is read or written."""
+    return _scrub(code, _code_stripes(code, stripes), "heal_ragged", valid=valid)
+
+
+def scrub_batch_host_ragged(code, stripes, valid):
+    """hrs_scrub_ragged_batch_host: scrub_stripes_ragged for stripes[S, n, L]
+    in HOST memory; staged memory sends only each cell's valid bytes."""
+    return _scrub_batch_host(code, stripes, "scrub_ragged", valid=valid)
+
+
+def heal_batch_host_ragged(code, stripes, valid):
+    """hrs_heal_ragged_batch_host: heal_stripes_ragged for stripes[S, n, L] in
+    HOST memory, healed in place; of staged memory only the valid bytes of the
+    cells that held a resolved error are written."""
+    return _scrub_batch_host(code, stripes, "heal_ragged", valid=valid)
+
+
+def heal_host_ragged(code, rows, valid):
+    """hrs_heal_ragged_host: heal_host with the stripe's n cell lengths; works
+    on host-only handles. Returns the report, a numpy uint32 array [4 + n]."""
+    n = code.stripeSize() + code.paritySize()
+    L = _host_stripe_rows(rows, n)
+    v = _ragged_valid(code, np.asarray(valid).reshape(1, -1), 1, n)
+    report = np.zeros(SCRUB_HEAD + n, dtype=np.uint32)
+    report[SCRUB_FIRST_BAD] = SCRUB_NONE
+    code._check(_lib.lib().hrs_heal_ragged_host(code._handle(), _lib.ptr_array([r.ctypes.data for r in rows]), L,
+                                                v.ctypes.data, report.ctypes.data))
     return report
 
 
